@@ -8,8 +8,11 @@ HBM before the timed region:
     -> (N>1) RCCL gradient all-reduce overlapped with backward -> global-norm clip -> AdamW
 (SURVEY.md §8(d) "primary metric").  The frozen LLM is NOT part of this path.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
-prints ONE JSON line on rank 0.  For N > 1 either launch it under torchrun (one rank per GPU; RANK / LOCAL_RANK /
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+prints ONE JSON line on rank 0.  A plain run sets up, warms up, times K steps and reports them (`value`,
+`ms_per_step`); `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy; `--full` adds the
+per-step spread, the kernel census / roofline leg, the CPU baseline and the extra.* variant and full-step figures.
+For N > 1 either launch it under torchrun (one rank per GPU; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment) or run it plainly: without WORLD_SIZE in the environment it re-executes
 itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`.
 """
@@ -140,7 +143,16 @@ def parse():
                     "instead of replaying the captured HIP graph")
     ap.add_argument("--cpu-threads", type=int, default=32, help="threads of the CPU baseline leg "
                     "(small GEMMs stop scaling well before a 2-socket host's 256 HW threads)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the per-step spread pass, "
+                    "the kernel census and roofline leg, the CPU baseline and, on a default run, the extra.* variant lines "
+                    "and full-step figures.  Off: set up, warm up, time --steps steps, dump outputs if asked, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
+                    "timed step computed as DIR/<name>.npy (float32): loss, scene_embeds, obj_embeds (the frozen encoder's "
+                    "features), params (the trainable parameters after the update); at most 64 MB in all, a larger array "
+                    "is replaced by a fixed, seeded sample of its elements")
     args = ap.parse_args()
+    if args.dump_outputs and (args.full_step or args.llm_stack or args.llm_layer or args.cpu_ops):
+        ap.error("--dump-outputs applies to the headline hot-path step only")
     if args.batch is None:
         args.batch = 4 if args.full_step else 16
     args.pipeline = not args.no_pipeline
@@ -182,7 +194,7 @@ class Trainer:
     """The hot-path step.  Optimiser settings: optim/build.py + configs/msr3d.yaml:43-47
     (AdamW lr 3e-5, betas (0.9, 0.999), wd 0.05), grad clip 5.0 (leo_trainer.py:192-193)."""
 
-    def __init__(self, model, device, example_batch, E, use_graph, accum=1, micro=1):
+    def __init__(self, model, device, example_batch, E, use_graph, accum=1, micro=1, keep_output=False):
         from msr3d_amd.dp import FlatGradAllReduce
         from msr3d_amd.train_step import HotPathTrainStep
         self.model = model
@@ -198,6 +210,7 @@ class Trainer:
         else:
             self.opt = torch.optim.AdamW(params, lr=3e-5, betas=(0.9, 0.999), weight_decay=0.05)
         state = {}
+        self.outputs = state
 
         def loss_fn(out):
             # synthetic scalar loss on the projector output, L = mean(scene_embeds * w); its gradient
@@ -208,6 +221,9 @@ class Trainer:
                 g = torch.Generator(device="cpu").manual_seed(99)
                 state["w"] = torch.randn(tuple(y.shape), generator=g).to(y.device)
                 state["g"] = state["w"] / y.numel()
+            if keep_output:
+                # --dump-outputs: the captured step's output buffer (every replay rewrites it) or the last eager one
+                state["y_graph" if y.is_cuda and torch.cuda.is_current_stream_capturing() else "y_eager"] = y
             if not y.is_cuda:
                 return (y * state["w"]).sum() / y.numel()
             with torch.no_grad():
@@ -222,6 +238,55 @@ class Trainer:
 
     def step(self, batch, next_batch=None):
         return self.stepper(batch, next_batch)
+
+    def last_outputs(self):
+        """name -> tensor: what the last step computed (its loss, the projector output, the frozen encoder's features it
+        trained on, the trainable parameters after its update)."""
+        st = self.stepper
+        y = self.outputs.get("y_graph") if st.graph is not None else None
+        out = {"loss": st.loss.detach().reshape(1)}
+        if y is None:
+            y = self.outputs.get("y_eager")
+        if y is not None:
+            out["scene_embeds"] = y.detach()
+        if not st.unfrozen:
+            out["obj_embeds"] = st.static["obj_embeds"]
+        flat = getattr(self.opt, "flat_p", None)
+        out["params"] = flat if flat is not None else torch.cat([p.detach().reshape(-1) for p in self.dp.order])
+        return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """tensors (name -> tensor) -> out_dir/<name>.npy as float32 (float64 stays float64).  If they exceed
+    DUMP_BUDGET_BYTES together, every array above 1 M elements is replaced by the same fixed, seeded sample of its
+    flattened elements (sorted indices) on every run.  -> {name: {"shape", "dtype", "sampled"}}"""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for k, t in tensors.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        arrs[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in arrs.values())
+    big = {k for k, a in arrs.items() if a.size > (1 << 20)}
+    scale = 1.0
+    if total > DUMP_BUDGET_BYTES and big:
+        small = sum(a.nbytes for k, a in arrs.items() if k not in big)
+        scale = 0.99 * (DUMP_BUDGET_BYTES - small) / sum(arrs[k].nbytes for k in big)
+    info = {}
+    for k, a in arrs.items():
+        sampled = None
+        if scale < 1.0 and k in big:
+            n = int(a.size * scale)
+            rng = np.random.default_rng([1234, zlib.crc32(k.encode())])
+            idx = np.sort(rng.choice(a.size, n, replace=False))
+            sampled = {"of": int(a.size), "kept": n, "seed": [1234, zlib.crc32(k.encode())]}
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        info[k] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": sampled}
+    return info
 
 
 def cpu_baseline(args, seconds):
@@ -841,7 +906,7 @@ def main():
     n_resident = 4 if calls == 1 else max(4, 2 * calls)     # (a window's micro-batches are distinct)
     batches = [synth_batch(1000 * rank + i, Bcall, O=O, P=P, device=device, dense=args.dense) for i in range(n_resident)]
     tr = Trainer(model, device, batches[0], args.llm_hidden, use_graph=not args.no_graph, accum=calls,
-                 micro=args.accum if wstep else 1)
+                 micro=args.accum if wstep else 1, keep_output=bool(args.dump_outputs))
 
     # Software pipelining (msr3d_amd/train_step.py): the frozen encoder of batch k+1 runs on a
     # side stream while batch k trains.  Every timed step still encodes exactly one batch and
@@ -961,17 +1026,19 @@ def main():
     elapsed = time.perf_counter() - t0
     if dist_on:
         tr.dp.timing = False          # (the exchange statistics below are the timed region's)
-    # per-step spread: the same steps again with an event record between them (up to 30; not part of `value`)
-    n_spread = min(args.steps, 30)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_spread + 1)]
-    marks[0].record()
-    for i in range(n_spread):
-        run_window(args.warmup + args.steps + i)
-        marks[i + 1].record()
-    torch.cuda.synchronize()
-    if dist_on:
-        dist.barrier()
-
+    dumped = dump_outputs(args.dump_outputs, tr.last_outputs()) if (args.dump_outputs and rank == 0) else None
+    marks = []
+    if args.full:
+        # per-step spread: the same steps again with an event record between them (up to 30; not part of `value`)
+        n_spread = min(args.steps, 30)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_spread + 1)]
+        marks[0].record()
+        for i in range(n_spread):
+            run_window(args.warmup + args.steps + i)
+            marks[i + 1].record()
+        torch.cuda.synchronize()
+        if dist_on:
+            dist.barrier()
 
     # MSR3D_DP_GRAPH_COMM=1: the RCCL call was captured with the rest, the step is one graph at N > 1 as well
     whole_graph = tr.stepper.graph is not None and not tr.stepper.split
@@ -1004,7 +1071,8 @@ def main():
     # of the library bracketed by HIP events on the launching stream (msr3d_amd/_lib.py::_Entry) -> mean duration per
     # entry point and launches per step.  Run on every rank (the steps hold the gradient exchange), read on rank 0;
     # after the exchange statistics above were taken (its steps exchange gradients too).
-    census = kernel_census(tr, batches, args.census_steps, run_window, args.warmup + 2 * args.steps) if args.census_steps > 0 else {}
+    census = (kernel_census(tr, batches, args.census_steps, run_window, args.warmup + 2 * args.steps)
+              if args.full and args.census_steps > 0 else {})
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
@@ -1039,8 +1107,8 @@ def main():
             first = args.warmup + (1 if pipe else 0)    # (pipelined: step i encodes batch i + 1)
             counts = [int(batches[(first + i) % n_resident]["obj_masks"].sum()) for i in range(args.steps)]
             objs_per_launch = sum(counts) / max(len(counts), 1)
-        roof = None
-        if not args.unfrozen:
+        roof = None                  # (a plain run: the headline figure only)
+        if args.full and not args.unfrozen:
             net = model.visual_prompter.obj_encoder.pcd_net
             stats = [_fused.row_statistics(net, bt["obj_fts"].reshape(-1, P, 6)) for bt in batches]
             scale = (calls if window else 1)
@@ -1117,7 +1185,7 @@ def main():
             roof["timed"] = (f"kernel census: {args.census_steps} eager (no graph), un-pipelined steps after the timed region, HIP "
                              "events on the launching stream around EVERY launch; the timed region itself carries no events")
             roof["step_launch_us_sum"] = sum(r["us"] * r["launches_per_step"] for r in table.values())
-        else:
+        elif args.full:
             # variant line: the fused frozen-encoder launches are not on this path (the SharedMLPs run as
             # group_rows -> token GEMM -> BatchNorm(train) kernels under autograd); no roofline leg
             roof = {"bound": "mfma", "kernel": None, "achieved": None, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
@@ -1126,9 +1194,6 @@ def main():
             "metric": f"MSQA train samples/sec (whole node), {O} obj x {P} pts",
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "ms_per_step_percentiles": {"p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90),
-                                        "note": "HIP events on the compute stream between steps, this rank, in a pass of its own after the timed region "
-                                                "(an event record a step costs the step 3-5 us)"},
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
             "dtype": ("VARIANT (MSR3D_SA_MMA=split2): frozen encoder on 2-term bf16 splits, 3 MFMA products per product (~16 bits); "
@@ -1153,9 +1218,17 @@ def main():
                                   "pinned host memory, copied over PCIe every step" if args.host_inputs
                                   else "resident in HBM"),
                        "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "kernels_ms": kern_ms,
         }
+        if args.full:
+            line["ms_per_step_percentiles"] = {
+                "p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90),
+                "note": "HIP events on the compute stream between steps, this rank, in a pass of its own after the timed region "
+                        "(an event record a step costs the step 3-5 us)"}
+            line["roofline"] = roof
+            line["kernels_ms"] = kern_ms
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                                      "note": "what the last timed step computed, written after the timed region"}
         from msr3d_amd import hipops as _hipops
         if _hipops._attn_mma[0] != "f32":     # a LABELLED reduced-precision object attention (never the headline)
             line["dtype"] = (f"VARIANT (MSR3D_ATTN_MMA={_hipops._attn_mma[0]}): object-attention QK^T / PV "
@@ -1167,13 +1240,13 @@ def main():
             line["census_us"] = {k: [round(v["us"], 2), v["per_step"]] for k, v in sorted(census.items())}
         if comm is not None:
             line["comm"] = comm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, args.cpu_baseline_seconds)
         plain = not (dist_on or args.unfrozen or args.skip_padded or args.no_pipeline or args.from_store or args.host_inputs
                      or args.accum > 1 or args.no_graph or args.time_all_kernels or (O, P) != (60, 1024) or args.dense
                      or args.llm_hidden != 4096 or args.batch != 16 or args.no_cpu_baseline
                      or args.situation_type != "as_transform_for_objects")
-        if reduced and not args.unfrozen:
+        if args.full and reduced and not args.unfrozen:
             # how far the reduced variant's encoder output is from the fp32-accurate path, on the first resident batch
             net = model.visual_prompter.obj_encoder.pcd_net
             pts0 = batches[0]["obj_fts"].reshape(-1, P, 6)
@@ -1183,7 +1256,7 @@ def main():
                 y6 = _fused.forward(net, pts0).double()
                 _fused.set_sa_mma(prev)
             line.setdefault("extra", {})["split2_rel_l2"] = float((y2 - y6).norm() / y6.norm())
-        if plain and not args.no_extra and not reduced:
+        if args.full and plain and not args.no_extra and not reduced:
             # SURVEY 8(f) rank 4, where > 99 % of a real step's time lives: the FULL step of BASELINE configs[1] (prompter ->
             # llm_proj -> scatter -> 32 LoRA-Llama layers at the Vicuna-7B shapes -> head -> CE -> backward into the
             # prompter -> clip + AdamW), in this process, after the headline: labelled secondary figures, never `value`

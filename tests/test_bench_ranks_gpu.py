@@ -17,7 +17,7 @@ def test_bench_two_ranks_json_contract():
     env = dict(os.environ, MSR3D_BENCH_SINGLE_DEVICE="1", MSR3D_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29671", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "4"]
+           "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "4", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -45,7 +45,7 @@ def test_bench_multi_rank_schedule_over_rccl_with_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3",
-                          "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 1 and j["config"]["parallelism"] == "dp1"
@@ -64,7 +64,7 @@ def test_bench_reduce_scatter_all_gather_exchange_and_accumulation(micro_steps):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--batch", "4", "--accum", "5", "--no-cpu-baseline"] +
+                          "--batch", "4", "--accum", "5", "--no-cpu-baseline", "--full"] +
                          (["--micro-steps"] if micro_steps else []), env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -77,7 +77,7 @@ def test_bench_reduce_scatter_all_gather_exchange_and_accumulation(micro_steps):
 
 def test_bench_single_rank_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--batch", "2", "--cpu-baseline-seconds", "1"], cwd=ROOT,
+                          "--batch", "2", "--cpu-baseline-seconds", "1", "--full"], cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -91,11 +91,11 @@ def test_bench_single_rank_json_contract():
 
 
 def test_bench_default_line_carries_the_full_step_and_the_levels():
-    """The driver's invocation (no workload flags): the headline line carries the roofline of the slowest SharedMLP level
+    """`--full` without workload flags: the headline line carries the roofline of the slowest SharedMLP level
     with all three levels beside it (distinct-row FLOPs priced, nominal rate stated) and, measured in the same process, the
     FULL MSR3D step at 4 x 576 tokens with e4m3 and with bf16 projections as extra.full_step."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "2",
-                          "--cpu-baseline-seconds", "1"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                          "--cpu-baseline-seconds", "1", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     r = j["roofline"]
@@ -206,3 +206,36 @@ def test_bench_full_step_line():
     assert c["lora_parameters"] == 2 * (4 * 131072 + 3 * 241664) and c["grad_bytes"] > 4 * c["lora_parameters"]
     assert j["comm"]["ranks_seen"] == 1 and j["comm"]["collectives_per_step"] >= 2
     assert j["comm"]["replica_checksum_spread"] == 0.0 and j["comm"]["exchange_exposed_ms_per_step"] >= 0
+
+
+def _plain_run(out_dir):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                          "--dump-outputs", str(out_dir)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run reports the timed steps and nothing that takes runs of its own (census, spread pass, CPU baseline,
+    variants); --dump-outputs writes the last timed step's results, and the same arguments give the same inputs."""
+    import numpy as np
+    runs = [_plain_run(tmp_path / f"run{i}") for i in range(2)]
+    j = runs[0]
+    assert j["steps"] == 3 and j["warmup"] == 2 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 16 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in j, k
+    for k in ("roofline", "census_us", "cpu_baseline", "extra", "ms_per_step_percentiles", "kernels_ms"):
+        assert k not in j, k
+    arrays = [{n: np.load(tmp_path / f"run{i}" / f"{n}.npy") for n in ("loss", "scene_embeds", "obj_embeds", "params")}
+              for i in range(2)]
+    a = arrays[0]
+    assert set(j["dumped_outputs"]["arrays"]) == set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["scene_embeds"].shape == (16, 60, 4096) and a["obj_embeds"].shape == (16, 60, 768)
+    for n, x in a.items():
+        assert x.dtype == np.float32 and np.isfinite(x).all(), n
+        y = arrays[1][n].astype(np.float64)
+        assert np.linalg.norm(x - y) <= 1e-5 * max(np.linalg.norm(y), 1e-30), n     # same inputs, same results

@@ -4,7 +4,7 @@
 A=$1; B=$2; N=${3:-3}
 for i in $(seq $N); do
   for v in "$A" "$B"; do
-    env $v python bench.py --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | \
+    env $v python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | \
       python -c "import sys,json; j=json.loads(sys.stdin.read()); print('$v', round(j['ms_per_step'],4), round(j['ms_per_step_percentiles']['p50'],4))"
   done
 done

@@ -6,7 +6,7 @@ R=$1; shift
 for i in $(seq 1 $R); do
   for e in "$@"; do
     envs="${e%%--*}"; flags=""; [[ "$e" == *"--"* ]] && flags="${e#*-- }"
-    env $envs python bench.py --no-cpu-baseline --no-extra --census-steps 0 --steps 40 $flags 2>/dev/null | tail -1 | python -c "
+    env $envs python bench.py --full --no-cpu-baseline --no-extra --census-steps 0 --steps 40 $flags 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('%-72s %9.1f  %.4f  p50 %.4f' % ('$e' or 'default', d['value'], d['ms_per_step'], d['ms_per_step_percentiles']['p50']))"
   done

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 run() {
   local name=$1; shift
   (cd /tmp && rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$ROOT/$OUT/$name" -- \
-      python "$ROOT/bench.py" --steps 6 --warmup 3 --no-cpu-baseline > "$ROOT/$OUT/$name.log" 2>&1)
+      python "$ROOT/bench.py" --full --steps 6 --warmup 3 --no-cpu-baseline > "$ROOT/$OUT/$name.log" 2>&1)
 }
 run sq1 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAVES SQ_BUSY_CU_CYCLES
 run grbm GRBM_GUI_ACTIVE

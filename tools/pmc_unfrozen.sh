@@ -12,14 +12,14 @@ run() {
   # (one derived memory counter per pass: FETCH_SIZE + WRITE_SIZE together exceed what one pass can collect, and the
   #  profiler then aborts without exiting -- hence also the timeout)
   (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$ROOT/$OUT/$name" -- \
-      python "$ROOT/bench.py" --unfrozen --batch 16 --steps 4 --warmup 2 --no-cpu-baseline > "$ROOT/$OUT/$name.log" 2>&1)
+      python "$ROOT/bench.py" --full --unfrozen --batch 16 --steps 4 --warmup 2 --no-cpu-baseline > "$ROOT/$OUT/$name.log" 2>&1)
 }
 run fetch FETCH_SIZE
 run write WRITE_SIZE
 run sq1 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA
 run grbm GRBM_GUI_ACTIVE
 (cd /tmp && timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/kt" -- \
-    python "$ROOT/bench.py" --unfrozen --batch 16 --steps 4 --warmup 2 --no-cpu-baseline > "$ROOT/$OUT/kt.log" 2>&1)
+    python "$ROOT/bench.py" --full --unfrozen --batch 16 --steps 4 --warmup 2 --no-cpu-baseline > "$ROOT/$OUT/kt.log" 2>&1)
 python - "$ROOT/$OUT" <<'PY'
 import csv, glob, re, sys, collections
 out = sys.argv[1]
