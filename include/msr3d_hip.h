@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 29
+#define MSR3D_ABI_VERSION 30
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1093,6 +1093,70 @@ typedef struct {
   int r, K, N, pad_;
 } msr3d_lora_shadow_job_t;
 int msr3d_lora_shadows(int njobs, const msr3d_lora_shadow_job_t *jobs_device, msr3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * KV-cached decoding of the LoRA-Llama stack (csrc/llm_decode.hip; msr3d_amd/llm/generate.py): what transformers'
+ * `generate` runs per new token, for up to MSR3D_SKINNY_MAX_M live rows (batch x beams).  bf16 storage, fp32
+ * accumulation, no atomics (bit-reproducible).  Lengths, positions and token ids are read from DEVICE memory -- a step
+ * never synchronises with the host -- and are range-checked in the kernel before they form an address: an index outside
+ * its range writes nothing.
+ *
+ * msr3d_bf16_skinny_lowrank: for each of njobs <= 3 weights that read the SAME activations,
+ *   C_j (M, N_j) bf16 = P W_j^T + P2 B2_j^T, operands as msr3d_bf16_gemm_lowrank's (P (M, K), W_j (N_j, K), P2 (M, R) =
+ *   s P A^T, B2_j (N_j, R) zero-padded, all k-contiguous bf16; R = 0 or B2_j NULL: no low-rank term for that job).
+ *   M <= MSR3D_SKINNY_MAX_M, K % 128 == 0, R % 32 == 0, N_j % 16 == 0, leading dimensions % 8 == 0, 16-byte aligned.
+ *   Every byte of W is read once per call (non-temporally), 16 or 32 of its rows per workgroup, the four waves of a
+ *   workgroup splitting K; v_mfma_f32_16x16x32_bf16 with the activations as the 16-row side.  q / k / v are one call
+ *   (njobs = 3).  swiglu != 0: njobs == 2 (gate, up; N_0 == N_1) and C_0 = bf16(silu(bf16 gate)) * bf16 up, the
+ *   roundings of msr3d_swiglu_fwd on bf16 projections; C_1 is not written.  `jobs` is HOST memory, read during the call.
+ * msr3d_rope_positions: x0 and (optional) x1 (B, T, H, D) bf16 rotated in place by pos (B, T) int32 (clamped to
+ *   0 .. table_rows - 1); cos / sin (table_rows, D) f32 as msr3d_rope_inplace reads; D % 16 == 0.  pos == arange(T): the
+ *   bits of msr3d_rope_inplace2.
+ * msr3d_rope_kv_append: a step's fresh q, k, v (N, H D) bf16 with row stride ld (they may be three column blocks of one
+ *   buffer): q rotated in place by pos[n]; rotated k and v written to slot len[n] of k_cache / v_cache (N, Tmax, H, D)
+ *   (len[n] outside 0 .. Tmax - 1: the cache is not written).  len is not advanced: one counter serves every layer.
+ * msr3d_attn_decode: out[n] (H D) bf16 = softmax(scale q[n] K^T + key padding) V per head over the keys
+ *   0 .. len[n] + len_add - 1 (clamped to Tmax) of row n's cache, any length; key_keep (N, Tmax) bytes, 0 = padded
+ *   key, or NULL; a row with no visible key gives 0.  D = 64 or 128.  A (row, head)'s keys are split over the four
+ *   waves of a workgroup and, with a workspace, over msr3d_attn_decode_splits(N, H) workgroups whose partial
+ *   (max, sum, out) a second launch merges in split order; workspace_floats >= N H splits (D + 2), or workspace NULL.
+ * msr3d_kv_reorder: beam search's gather dst[p][n][t] = src[p][beam_idx[n]][t], t < len[beam_idx[n]], over all
+ *   `planes` (layers x {k, v}) of a (planes, N, Tmax, row_elems) bf16 cache in one launch; src != dst (two buffers
+ *   ping-ponged); len describes the SOURCE rows; row_elems % 8 == 0.
+ * msr3d_decode_select: per row n of logits (N, V) bf16 the top k (value, token) pairs, ties to the lower token, of
+ *   order 0 (greedy):  log_softmax(processors(logits)) + beam_score[n]
+ *   order 1 (beams):   processors(log_softmax(logits)) + beam_score[n]           (transformers' two decoding loops)
+ *   processors = repetition penalty over prev_tokens[n][0 .. n_prev[n] - 1] (int64, row stride ld_prev; x < 0 ? x p : x / p,
+ *   once per distinct token) then eos_id -> -inf while n_prev[n] < min_length.  beam_score NULL = 0; n_prev NULL = 0.
+ *   V <= MSR3D_DECODE_SELECT_MAX_V (the row lives in LDS as fp32), k <= MSR3D_DECODE_SELECT_MAX_K.  out_val, out_tok (N, k).
+ * ------------------------------------------------------------------------- */
+#define MSR3D_SKINNY_MAX_M 32
+#define MSR3D_ATTN_DECODE_MAX_SPLITS 8
+#define MSR3D_DECODE_SELECT_MAX_V 40000
+#define MSR3D_DECODE_SELECT_MAX_K 64
+typedef struct {
+  const void *W; int ldw;      /* (N, K) bf16 */
+  const void *B2; int ldb2;    /* (N, R) bf16 or NULL */
+  void *C; int ldc;            /* (M, N) bf16 */
+  int N;
+} msr3d_skinny_job_t;
+int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                              const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
+int msr3d_rope_positions(int B, int T, int H, int D, void *x0, void *x1, const int *pos, const float *cos_td,
+                         const float *sin_td, int table_rows, msr3d_stream_t stream);
+int msr3d_rope_kv_append(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,
+                         const int *len, const float *cos_td, const float *sin_td, int table_rows, void *k_cache,
+                         void *v_cache, msr3d_stream_t stream);
+int msr3d_attn_decode_splits(int N, int H);
+int msr3d_attn_decode(int N, int Tmax, int H, int D, const void *q, int ldq, const void *k_cache, const void *v_cache,
+                      const int *len, int len_add, const unsigned char *key_keep, float scale, void *out, int ldo,
+                      float *workspace, long long workspace_floats, msr3d_stream_t stream);
+int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src, void *dst, const int *beam_idx,
+                     const int *len, msr3d_stream_t stream);
+int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,
+                        const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
+                        int order, int k, float *out_val, int *out_tok, msr3d_stream_t stream);
+
 
 
 /* ---------------------------------------------------------------------------

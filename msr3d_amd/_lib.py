@@ -53,6 +53,11 @@ class LoraGradJob(ctypes.Structure):
                 ("transpose_out", _c_int)]
 
 
+class SkinnyJob(ctypes.Structure):
+    """msr3d_skinny_job_t (include/msr3d_hip.h)."""
+    _fields_ = [("W", _ptr), ("ldw", _c_int), ("B2", _ptr), ("ldb2", _c_int), ("C", _ptr), ("ldc", _c_int), ("N", _c_int)]
+
+
 class LoraShadowJob(ctypes.Structure):
     """msr3d_lora_shadow_job_t (include/msr3d_hip.h)."""
     _fields_ = [("A", _ptr), ("B", _ptr), ("a_pad", _ptr), ("b2", _ptr), ("bt_pad", _ptr), ("at2", _ptr),
@@ -152,6 +157,17 @@ _SIGNATURES = {
                         ctypes.c_longlong, _ptr],
     "msr3d_lora_grad_pair": [_c_int, _c_int, _c_int, ctypes.POINTER(LoraGradJob), _c_float, _c_int, _ptr],
     "msr3d_lora_shadows": [_c_int, _ptr, _ptr],
+    "msr3d_bf16_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, ctypes.POINTER(SkinnyJob),
+                                  _c_int, _ptr],
+    "msr3d_rope_positions": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
+    "msr3d_rope_kv_append": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr,
+                             _ptr, _ptr],
+    "msr3d_attn_decode_splits": [_c_int, _c_int],
+    "msr3d_attn_decode": [_c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _c_float, _ptr,
+                          _c_int, _ptr, ctypes.c_longlong, _ptr],
+    "msr3d_kv_reorder": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "msr3d_decode_select": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,
+                            _c_int, _ptr, _ptr, _ptr],
     "msr3d_attn_fwd": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _c_float, _ptr, _ptr, _ptr],
     "msr3d_attn_bwd": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_float, _ptr, _ptr,
                        _ptr, _ptr, _ptr, _ptr],
@@ -255,7 +271,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form", "msr3d_attn_fwd_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 29        # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 30        # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():

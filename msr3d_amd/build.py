@@ -46,6 +46,7 @@ SOURCES = [
     ("lora_fp8.hip", []),
     ("llm_layer.hip", []),
     ("llm_attn.hip", []),
+    ("llm_decode.hip", []),
     ("prompter_rows.hip", ["-ffp-contract=off"]),
     ("anchor_front.hip", ["-ffp-contract=off"]),
     ("scene_block.hip", []),

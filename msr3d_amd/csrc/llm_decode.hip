@@ -1,0 +1,658 @@
+// llm_decode.hip -- the kernels of one KV-cached decoding step of the LoRA-Llama stack (msr3d_amd/llm/generate.py):
+// what transformers' `generate` runs per new token, for N <= 32 live rows (batch x beams).
+//
+//     msr3d_bf16_skinny_lowrank   C (M <= 32, N) = P W^T + P2 B2^T      every projection and the head: a weight stream
+//     msr3d_rope_kv_append        rotate q, k by the row's own position, write k, v into cache slot len[n]
+//     msr3d_rope_positions        the prefill twin: (B, T, H, D) rotated by pos (B, T)
+//     msr3d_attn_decode           one query row per (row, head) against the row's cache: a stream over K and V
+//     msr3d_kv_reorder            beam search's cache gather, every layer in one launch
+//     msr3d_decode_select         logits processors + log-softmax + the row's top-k candidates
+//
+// bf16 storage, fp32 accumulation.  Nothing here uses atomics: every output has one owner and partial results are
+// merged in a fixed order, so a step is bit-reproducible.  Lengths and positions are read from device memory (a step
+// has no host synchronisation) and every index read from memory is range-checked before it forms an address.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/msr3d_hip.h"
+
+namespace {
+
+using u16 = unsigned short;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
+__device__ __forceinline__ u16 f2bf(float f) {
+  unsigned u = __float_as_uint(f);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (u16)(u >> 16);
+}
+__device__ __forceinline__ void unpack8(uint4 v, float (&f)[8]) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+  unsigned w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) w[i] = (unsigned)f2bf(f[2 * i]) | ((unsigned)f2bf(f[2 * i + 1]) << 16);
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// a 16-byte piece of a weight: read once per call and never again -- non-temporal, so the stream does not push the
+// activations and the K / V cache out of L2
+__device__ __forceinline__ u32x4 load_stream(const u16 *p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+}
+__device__ __forceinline__ u32x4 load_keep(const u16 *p) { return *reinterpret_cast<const u32x4 *>(p); }
+__device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// ---- skinny product -------------------------------------------------------------------------------------------
+// v_mfma_f32_16x16x32_bf16 with the ACTIVATIONS as the 16-row side: lane l supplies P[row l & 15][k0 + 8 (l >> 4) + j] and
+// W[n0 + (l & 15)][k0 + 8 (l >> 4) + j], j < 8 -- for W that is 16 contiguous bytes of a k-contiguous weight row, loaded
+// straight from memory into the operand registers (no LDS: nothing of W is shared between waves).  A workgroup of four
+// waves owns 16 TN rows of W; the waves split K in 128-wide chunks, keep the loads of the next chunk in flight while the
+// matrix pipe works on this one, and add their partial sums through LDS in wave order.  The activations (M rows, a few
+// hundred KB at most) are read from L2 by every workgroup -- 32 x 11008 bf16 do not fit the 160 KB of LDS, and staging
+// K in slices would put a barrier into the weight stream.
+struct SkinnyJobs {
+  const u16 *W[3];
+  const u16 *B2[3];
+  u16 *C[3];
+  int N[3];
+  int ldw[3], ldb2[3], ldc[3];
+  int tiles[3];      // exclusive prefix sums of the jobs' tile counts are formed in the kernel (njobs <= 3)
+  int njobs;
+};
+
+template <int MT, int TN, bool SWIGLU>
+__global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const u16 *__restrict__ P, int ldp,
+                                                     const u16 *__restrict__ P2, int ldp2, SkinnyJobs jobs) {
+  __shared__ float red[4][MT * TN][64][4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r16 = lane & 15, g = lane >> 4;
+  int tile = blockIdx.x, job = 0;
+  if (!SWIGLU) {
+    while (job + 1 < jobs.njobs && tile >= jobs.tiles[job]) { tile -= jobs.tiles[job]; ++job; }
+  }
+  // SWIGLU: job 0 = gate, job 1 = up, the workgroup takes the SAME 16 rows of both (TN == 2 is the job index)
+  const u16 *wrow[TN];
+  const u16 *brow[TN];
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const int j = SWIGLU ? t : job;
+    const int n = SWIGLU ? tile * 16 + r16 : (tile * TN + t) * 16 + r16;
+    wrow[t] = jobs.W[j] + (size_t)n * jobs.ldw[j] + 8 * g;
+    brow[t] = jobs.B2[j] ? jobs.B2[j] + (size_t)n * jobs.ldb2[j] + 8 * g : nullptr;
+  }
+  const u16 *prow[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int row = min(m * 16 + r16, M - 1);       // rows >= M: a valid row is read and its result not stored
+    prow[m] = P + (size_t)row * ldp + 8 * g;
+  }
+  f32x4 acc[MT][TN];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int t = 0; t < TN; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int chunks = K >> 7;
+  const int c0 = (chunks * wave) >> 2, c1 = (chunks * (wave + 1)) >> 2;
+  u32x4 w[TN][4], a[MT][4];
+  if (c0 < c1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int t = 0; t < TN; ++t) w[t][i] = load_stream(wrow[t] + (size_t)c0 * 128 + 32 * i);
+#pragma unroll
+      for (int m = 0; m < MT; ++m) a[m][i] = load_keep(prow[m] + (size_t)c0 * 128 + 32 * i);
+    }
+  }
+  for (int c = c0; c < c1; ++c) {
+    u32x4 wn[TN][4], an[MT][4];
+    if (c + 1 < c1) {                               // (wave-uniform: the next chunk's loads go out before this one's MFMAs)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int t = 0; t < TN; ++t) wn[t][i] = load_stream(wrow[t] + (size_t)(c + 1) * 128 + 32 * i);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) an[m][i] = load_keep(prow[m] + (size_t)(c + 1) * 128 + 32 * i);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[m][t] = mfma(a[m][i], w[t][i], acc[m][t]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int t = 0; t < TN; ++t) w[t][i] = wn[t][i];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) a[m][i] = an[m][i];
+    }
+  }
+  if (wave == 3 && R > 0) {
+    // the low-rank pair rides as R / 32 extra k steps: P2 (M, R) = s P A^T, B2 (N, R) = B, zero-padded
+    for (int k = 0; k < R; k += 32) {
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const int row = min(m * 16 + r16, M - 1);
+        const u32x4 pa = load_keep(P2 + (size_t)row * ldp2 + 8 * g + k);
+#pragma unroll
+        for (int t = 0; t < TN; ++t)
+          if (brow[t]) acc[m][t] = mfma(pa, load_keep(brow[t] + k), acc[m][t]);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[wave][m * TN + t][lane][i] = acc[m][t][i];
+  __syncthreads();
+  // accumulator element i of lane l is C[row 4 (l >> 4) + i][column l & 15]; the four waves' partial sums in wave order
+  if (SWIGLU) {
+    for (int e = threadIdx.x; e < MT * 256; e += 256) {
+      const int m = e >> 8, l = (e >> 2) & 63, i = e & 3;
+      const int row = m * 16 + 4 * (l >> 4) + i, col = l & 15;
+      if (row >= M) continue;
+      float gsum = 0.f, usum = 0.f;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) { gsum += red[wv][m * TN + 0][l][i]; usum += red[wv][m * TN + (TN - 1)][l][i]; }
+      // the same roundings as the training graph: gate and up are bf16 tensors, silu a bf16 op of its own
+      const float gb = bf2f(f2bf(gsum)), ub = bf2f(f2bf(usum));
+      const float sg = bf2f(f2bf(gb / (1.0f + expf(-gb))));
+      jobs.C[0][(size_t)row * jobs.ldc[0] + tile * 16 + col] = f2bf(sg * ub);
+    }
+  } else {
+    for (int e = threadIdx.x; e < MT * TN * 256; e += 256) {
+      const int mt = e >> 8, l = (e >> 2) & 63, i = e & 3;
+      const int m = mt / TN, t = mt % TN;
+      const int row = m * 16 + 4 * (l >> 4) + i, col = l & 15;
+      if (row >= M) continue;
+      float s = 0.f;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) s += red[wv][mt][l][i];
+      jobs.C[job][(size_t)row * jobs.ldc[job] + (tile * TN + t) * 16 + col] = f2bf(s);
+    }
+  }
+}
+
+// ---- rotary embedding by explicit positions ------------------------------------------------------------------
+// The arithmetic of rope_vec_kernel (llm_layer.hip), operation for operation: where pos is arange the results are
+// the same bits (tests/test_llm_decode_gpu.py holds the two together).  A thread owns eight adjacent pairs of one head.
+struct RopeCoef {
+  float c1[8], c2[8], s1[8], s2[8];
+};
+__device__ __forceinline__ RopeCoef rope_coef(const float *__restrict__ cs, const float *__restrict__ sn, int t, int D, int i0) {
+  RopeCoef r;
+  const int half = D >> 1;
+  const float *cr = cs + (size_t)t * D + i0, *sr = sn + (size_t)t * D + i0;
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const float4 a = *reinterpret_cast<const float4 *>(cr + 4 * v), b = *reinterpret_cast<const float4 *>(cr + half + 4 * v);
+    const float4 e = *reinterpret_cast<const float4 *>(sr + 4 * v), f = *reinterpret_cast<const float4 *>(sr + half + 4 * v);
+    r.c1[4 * v] = a.x; r.c1[4 * v + 1] = a.y; r.c1[4 * v + 2] = a.z; r.c1[4 * v + 3] = a.w;
+    r.c2[4 * v] = b.x; r.c2[4 * v + 1] = b.y; r.c2[4 * v + 2] = b.z; r.c2[4 * v + 3] = b.w;
+    r.s1[4 * v] = e.x; r.s1[4 * v + 1] = e.y; r.s1[4 * v + 2] = e.z; r.s1[4 * v + 3] = e.w;
+    r.s2[4 * v] = f.x; r.s2[4 * v + 1] = f.y; r.s2[4 * v + 2] = f.z; r.s2[4 * v + 3] = f.w;
+  }
+  return r;
+}
+__device__ __forceinline__ void rope_rotate(const RopeCoef &r, uint4 va, uint4 vb, uint4 &oa, uint4 &ob) {
+  float a[8], b[8], ya[8], yb[8];
+  unpack8(va, a);
+  unpack8(vb, b);
+  {
+    // the contraction rope_vec_kernel compiles to, pinned: the second product rounded, the first fused into the sum
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      ya[e] = fmaf(a[e], r.c1[e], -(b[e] * r.s1[e]));
+      yb[e] = fmaf(b[e], r.c2[e], a[e] * r.s2[e]);
+    }
+  }
+  oa = pack8(ya);
+  ob = pack8(yb);
+}
+
+__global__ __launch_bounds__(256) void rope_positions_kernel(long long n_items, int H, int D, u16 *__restrict__ x0,
+                                                             u16 *__restrict__ x1, const int *__restrict__ pos, int table_rows,
+                                                             const float *__restrict__ cs, const float *__restrict__ sn) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;     // one (b t, h, 16-dim piece) per thread
+  if (id >= n_items) return;
+  const int half = D >> 1, npc = D >> 4;
+  const int c = (int)(id % npc);
+  const int h = (int)((id / npc) % H);
+  const long long bt = id / ((long long)npc * H);
+  const int t = min(max(pos[bt], 0), table_rows - 1);
+  const RopeCoef r = rope_coef(cs, sn, t, D, 8 * c);
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    u16 *x = which ? x1 : x0;
+    if (!x) continue;
+    u16 *row = x + (bt * H + h) * D + 8 * c;
+    uint4 oa, ob;
+    rope_rotate(r, *reinterpret_cast<const uint4 *>(row), *reinterpret_cast<const uint4 *>(row + half), oa, ob);
+    *reinterpret_cast<uint4 *>(row) = oa;
+    *reinterpret_cast<uint4 *>(row + half) = ob;
+  }
+}
+
+__global__ __launch_bounds__(256) void rope_kv_append_kernel(int n_items, int H, int D, int Tmax, u16 *__restrict__ q,
+                                                             const u16 *__restrict__ k, const u16 *__restrict__ v, int ld,
+                                                             const int *__restrict__ pos, const int *__restrict__ len,
+                                                             int table_rows, const float *__restrict__ cs,
+                                                             const float *__restrict__ sn, u16 *__restrict__ kc,
+                                                             u16 *__restrict__ vc) {
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= n_items) return;
+  const int half = D >> 1, npc = D >> 4;
+  const int c = id % npc, h = (id / npc) % H, n = id / (npc * H);
+  const int t = min(max(pos[n], 0), table_rows - 1);
+  const int slot = len[n];
+  const RopeCoef r = rope_coef(cs, sn, t, D, 8 * c);
+  const size_t src = (size_t)n * ld + (size_t)h * D + 8 * c;
+  uint4 oa, ob;
+  rope_rotate(r, *reinterpret_cast<const uint4 *>(q + src), *reinterpret_cast<const uint4 *>(q + src + half), oa, ob);
+  *reinterpret_cast<uint4 *>(q + src) = oa;
+  *reinterpret_cast<uint4 *>(q + src + half) = ob;
+  if (slot < 0 || slot >= Tmax) return;             // a full cache: nothing is written outside it
+  rope_rotate(r, *reinterpret_cast<const uint4 *>(k + src), *reinterpret_cast<const uint4 *>(k + src + half), oa, ob);
+  const size_t dst = (((size_t)n * Tmax + slot) * H + h) * D + 8 * c;
+  *reinterpret_cast<uint4 *>(kc + dst) = oa;
+  *reinterpret_cast<uint4 *>(kc + dst + half) = ob;
+  *reinterpret_cast<uint4 *>(vc + dst) = *reinterpret_cast<const uint4 *>(v + src);
+  *reinterpret_cast<uint4 *>(vc + dst + half) = *reinterpret_cast<const uint4 *>(v + src + half);
+}
+
+// ---- decode attention -------------------------------------------------------------------------------------------
+// grid (H, N, S): split s of (row n, head h) takes the keys [s L / S, (s + 1) L / S) of the row's L = len[n] + len_add.
+// A key's D values are 16-byte pieces over D / 8 lanes, so a wave reads 64 / (D / 8) keys per step (4 at D = 128, 8 at
+// 64) and its four waves interleave those steps; every lane group carries its own online-softmax state (max, sum,
+// eight output values), merged over the wave's groups by shuffles, over the waves through LDS in wave order and -- when
+// S > 1 -- over the splits by attn_merge_kernel in split order.  exp2 throughout, the scale folded with log2 e.
+constexpr float kNegBig = -1.0e30f;
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const u16 *__restrict__ q, int ldq,
+                                                          const u16 *__restrict__ kc, const u16 *__restrict__ vc,
+                                                          const int *__restrict__ len, int len_add,
+                                                          const unsigned char *__restrict__ keep, float scale_log2,
+                                                          u16 *__restrict__ out, int ldo, float *__restrict__ part) {
+  constexpr int LPK = D / 8, KPW = 64 / LPK;
+  __shared__ float sm[4], sl[4], so[4][D];
+  const int h = blockIdx.x, n = blockIdx.y, s = blockIdx.z, S = gridDim.z;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int piece = lane % LPK, grp = lane / LPK;
+  const int L = min(max(len[n] + len_add, 0), Tmax);
+  const int t0 = (int)(((long long)L * s) / S), t1 = (int)(((long long)L * (s + 1)) / S);
+  float qf[8];
+  unpack8(*reinterpret_cast<const uint4 *>(q + (size_t)n * ldq + (size_t)h * D + 8 * piece), qf);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) qf[e] *= scale_log2;
+  float m = kNegBig, l = 0.f, o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  const size_t row0 = (size_t)n * Tmax;
+  const unsigned char *kp = keep ? keep + row0 : nullptr;
+  constexpr int U = 4;
+  for (int tb = t0 + wave * KPW; tb < t1; tb += 4 * KPW * U) {
+    uint4 kv[U], vv[U];
+    bool on[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int t = tb + u * 4 * KPW + grp;
+      on[u] = t < t1 && (!kp || kp[t]);
+      const size_t off = ((row0 + (on[u] ? t : t0)) * H + h) * D + 8 * piece;     // (t0 < t1 <= Tmax here: in bounds)
+      kv[u] = *reinterpret_cast<const uint4 *>(kc + off);
+      vv[u] = *reinterpret_cast<const uint4 *>(vc + off);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float kf[8], vf[8];
+      unpack8(kv[u], kf);
+      unpack8(vv[u], vf);
+      float sc = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sc += qf[e] * kf[e];
+#pragma unroll
+      for (int x = 1; x < LPK; x <<= 1) sc += __shfl_xor(sc, x);
+      if (on[u]) {
+        const float mn = fmaxf(m, sc);
+        const float f = exp2f(m - mn), p = exp2f(sc - mn);
+        l = l * f + p;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = o[e] * f + p * vf[e];
+        m = mn;
+      }
+    }
+  }
+  // the wave's lane groups (same dims, different keys): butterfly over the group index -- every lane of a dim ends with the
+  // same value, in an order fixed by the lane numbers
+#pragma unroll
+  for (int x = LPK; x < 64; x <<= 1) {
+    const float m2 = __shfl_xor(m, x), l2 = __shfl_xor(l, x);
+    const float mn = fmaxf(m, m2);
+    // (both factors from the lower and the upper partner in the same roles on both sides: a + b with a from the lower lane)
+    const bool low = (lane & x) == 0;
+    const float fa = exp2f((low ? m : m2) - mn), fb = exp2f((low ? m2 : m) - mn);
+    l = (low ? l : l2) * fa + (low ? l2 : l) * fb;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float o2 = __shfl_xor(o[e], x);
+      o[e] = (low ? o[e] : o2) * fa + (low ? o2 : o[e]) * fb;
+    }
+    m = mn;
+  }
+  if (grp == 0) {
+    if (piece == 0) { sm[wave] = m; sl[wave] = l; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) so[wave][8 * piece + e] = o[e];
+  }
+  __syncthreads();
+  if (threadIdx.x < D) {
+    const int d = threadIdx.x;
+    float mm = sm[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) mm = fmaxf(mm, sm[w]);
+    float ll = 0.f, oo = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = exp2f(sm[w] - mm);
+      ll += sl[w] * f;
+      oo += so[w][d] * f;
+    }
+    if (part) {
+      float *pp = part + (((size_t)n * H + h) * S + s) * (D + 2);
+      if (d == 0) { pp[0] = mm; pp[1] = ll; }
+      pp[2 + d] = oo;
+    } else {
+      out[(size_t)n * ldo + (size_t)h * D + d] = f2bf(ll > 0.f ? oo / ll : 0.f);       // no visible key: 0
+    }
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(D) void attn_merge_kernel(int H, int S, const float *__restrict__ part, u16 *__restrict__ out,
+                                                       int ldo) {
+  const int h = blockIdx.x, n = blockIdx.y, d = threadIdx.x;
+  const float *pp = part + ((size_t)n * H + h) * S * (D + 2);
+  float mm = kNegBig;
+  for (int s = 0; s < S; ++s) mm = fmaxf(mm, pp[(size_t)s * (D + 2)]);
+  float ll = 0.f, oo = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const float f = exp2f(pp[(size_t)s * (D + 2)] - mm);
+    ll += pp[(size_t)s * (D + 2) + 1] * f;
+    oo += pp[(size_t)s * (D + 2) + 2 + d] * f;
+  }
+  out[(size_t)n * ldo + (size_t)h * D + d] = f2bf(ll > 0.f ? oo / ll : 0.f);
+}
+
+// ---- cache gather -----------------------------------------------------------------------------------------------
+// dst[p][n][t] = src[p][idx[n]][t], t < len[idx[n]], for every plane p (layers x {k, v}); 16-byte pieces.
+__global__ __launch_bounds__(256) void kv_reorder_kernel(int N, int Tmax, int row_vec, const uint4 *__restrict__ src,
+                                                         uint4 *__restrict__ dst, const int *__restrict__ idx,
+                                                         const int *__restrict__ len) {
+  const int n = blockIdx.y, p = blockIdx.z;
+  const int from = idx[n];
+  if (from < 0 || from >= N) return;                 // not a row of the cache: nothing is read or written
+  const long long count = (long long)min(max(len[from], 0), Tmax) * row_vec;
+  const uint4 *s = src + ((size_t)p * N + from) * Tmax * row_vec;
+  uint4 *d = dst + ((size_t)p * N + n) * Tmax * row_vec;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) d[i] = s[i];
+}
+
+// ---- candidate selection ----------------------------------------------------------------------------------------
+// One workgroup per row, the row's V scores in LDS as fp32.  order 0 (greedy, transformers' _sample): the processors act
+// on the raw logits, then log-softmax; order 1 (transformers' _beam_search): log-softmax first, the processors on the
+// log-probabilities.  Then + beam_score[n] and k rounds of arg-max, ties to the lower token id.
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+__global__ __launch_bounds__(256) void decode_select_kernel(int V, const u16 *__restrict__ logits, int ldl,
+                                                            const long long *__restrict__ prev, int ldprev,
+                                                            const int *__restrict__ n_prev, int prev_cap, float penalty,
+                                                            int min_length, int eos, const float *__restrict__ beam_score,
+                                                            int order, int k, float *__restrict__ out_val,
+                                                            int *__restrict__ out_tok) {
+  extern __shared__ float sc[];                     // the row's V scores
+  __shared__ float rv[4];
+  __shared__ int ri[4];
+  __shared__ float bcast[2];
+  const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const u16 *lg = logits + (size_t)n * ldl;
+  const int np = n_prev ? min(max(n_prev[n], 0), prev_cap) : 0;
+  const long long *pv = prev + (size_t)n * ldprev;
+  for (int v = tid; v < V; v += 256) sc[v] = bf2f(lg[v]);
+  __syncthreads();
+  if (order == 0) {
+    // every occurrence of a token writes the same value (computed from the unprocessed logit): applied once
+    if (penalty != 1.0f)
+      for (int i = tid; i < np; i += 256) {
+        const long long t = pv[i];
+        if (t < 0 || t >= V) continue;
+        const float x = bf2f(lg[t]);
+        sc[t] = x < 0.f ? x * penalty : x / penalty;
+      }
+    __syncthreads();
+    if (tid == 0 && np < min_length && eos >= 0 && eos < V) sc[eos] = -INFINITY;
+    __syncthreads();
+  }
+  // log-softmax of what is in sc
+  float mx = -INFINITY;
+  for (int v = tid; v < V; v += 256) mx = fmaxf(mx, sc[v]);
+  for (int x = 32; x > 0; x >>= 1) mx = fmaxf(mx, __shfl_xor(mx, x));
+  if (lane == 0) rv[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int v = tid; v < V; v += 256) sum += expf(sc[v] - mx);
+  for (int x = 32; x > 0; x >>= 1) sum += __shfl_xor(sum, x);
+  if (lane == 0) rv[wave] = sum;
+  __syncthreads();
+  if (tid == 0) bcast[0] = mx + logf(((rv[0] + rv[1]) + rv[2]) + rv[3]);
+  __syncthreads();
+  const float lse = bcast[0];
+  const float add = beam_score ? beam_score[n] : 0.f;
+  if (order == 0) {
+    for (int v = tid; v < V; v += 256) sc[v] = (sc[v] - lse) + add;
+    __syncthreads();
+  } else {
+    for (int v = tid; v < V; v += 256) sc[v] = sc[v] - lse;
+    __syncthreads();
+    if (penalty != 1.0f) {
+      for (int i = tid; i < np; i += 256) {
+        const long long t = pv[i];
+        if (t < 0 || t >= V) continue;
+        const float x = bf2f(lg[t]) - lse;             // from the unprocessed value: every occurrence writes the same
+        sc[t] = x < 0.f ? x * penalty : x / penalty;
+      }
+    }
+    __syncthreads();
+    if (tid == 0 && np < min_length && eos >= 0 && eos < V) sc[eos] = -INFINITY;
+    __syncthreads();
+    for (int v = tid; v < V; v += 256) sc[v] += add;
+    __syncthreads();
+  }
+  for (int r = 0; r < k; ++r) {
+    float bv = -INFINITY;
+    int bi = V;                                       // V = nothing found yet (taken entries are NaN and never compare)
+    for (int v = tid; v < V; v += 256) {
+      const float x = sc[v];
+      if (x == x && (bi == V || better(x, v, bv, bi))) { bv = x; bi = v; }
+    }
+    for (int x = 32; x > 0; x >>= 1) {
+      const float ov = __shfl_xor(bv, x);
+      const int oi = __shfl_xor(bi, x);
+      if (oi < V && (bi == V || better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      bv = rv[0]; bi = ri[0];
+      for (int w = 1; w < 4; ++w)
+        if (ri[w] < V && (bi == V || better(rv[w], ri[w], bv, bi))) { bv = rv[w]; bi = ri[w]; }
+      out_val[(size_t)n * k + r] = bi < V ? bv : -INFINITY;
+      out_tok[(size_t)n * k + r] = bi < V ? bi : 0;
+      if (bi < V) sc[bi] = __int_as_float(0x7fc00000);
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                              const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
+  if (M < 0 || M > MSR3D_SKINNY_MAX_M || K <= 0 || (K % 128) || R < 0 || (R % 32) || njobs < 1 || njobs > 3 || !jobs)
+    return MSR3D_EINVAL;
+  if (!P || ldp < K || (ldp % 8) || !al16(P)) return MSR3D_EINVAL;
+  if (R > 0 && (!P2 || ldp2 < R || (ldp2 % 8) || !al16(P2))) return MSR3D_EINVAL;
+  if (swiglu && (njobs != 2 || jobs[0].N != jobs[1].N || !jobs[0].C)) return MSR3D_EINVAL;
+  // two 16-row tiles of W per workgroup where that still leaves every CU several workgroups (the activations are read
+  // once per workgroup); gate | up with the SwiGLU epilogue is always the pair
+  long long rows = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const msr3d_skinny_job_t &jb = jobs[j];
+    if (jb.N <= 0 || (jb.N % 16) || !jb.W || jb.ldw < K || (jb.ldw % 8) || !al16(jb.W)) return MSR3D_EINVAL;
+    if (R > 0 && jb.B2 && (jb.ldb2 < R || (jb.ldb2 % 8) || !al16(jb.B2))) return MSR3D_EINVAL;
+    if (!(swiglu && j == 1) && (!jb.C || jb.ldc < jb.N)) return MSR3D_EINVAL;
+    rows += jb.N;
+  }
+  if (M == 0) return 0;
+  int tn = (swiglu || rows >= 16384) ? 2 : 1;
+  if (!swiglu && tn == 2)
+    for (int j = 0; j < njobs; ++j)
+      if (jobs[j].N % 32) tn = 1;
+  SkinnyJobs sj{};
+  sj.njobs = njobs;
+  long long grid = 0;
+  for (int j = 0; j < njobs; ++j) {
+    sj.W[j] = (const u16 *)jobs[j].W; sj.B2[j] = R > 0 ? (const u16 *)jobs[j].B2 : nullptr; sj.C[j] = (u16 *)jobs[j].C;
+    sj.N[j] = jobs[j].N; sj.ldw[j] = jobs[j].ldw; sj.ldb2[j] = jobs[j].ldb2; sj.ldc[j] = jobs[j].ldc;
+    sj.tiles[j] = swiglu ? jobs[j].N / 16 : jobs[j].N / (16 * tn);
+    grid += sj.tiles[j];
+  }
+  if (swiglu) grid = sj.tiles[0];
+  hipStream_t st = (hipStream_t)stream;
+  const u16 *p = (const u16 *)P, *p2 = (const u16 *)P2;
+  const int mt = M <= 16 ? 1 : 2;
+#define MSR3D_SK(MT, TN, SW) skinny_kernel<MT, TN, SW><<<(unsigned)grid, 256, 0, st>>>(M, K, R, p, ldp, p2, ldp2, sj)
+  if (swiglu) { if (mt == 1) MSR3D_SK(1, 2, true); else MSR3D_SK(2, 2, true); }
+  else if (tn == 2) { if (mt == 1) MSR3D_SK(1, 2, false); else MSR3D_SK(2, 2, false); }
+  else { if (mt == 1) MSR3D_SK(1, 1, false); else MSR3D_SK(2, 1, false); }
+#undef MSR3D_SK
+  return (int)hipGetLastError();
+}
+
+int msr3d_rope_positions(int B, int T, int H, int D, void *x0, void *x1, const int *pos, const float *cos_td,
+                         const float *sin_td, int table_rows, msr3d_stream_t stream) {
+  if (B < 0 || T <= 0 || H <= 0 || D <= 0 || (D % 16) || table_rows <= 0) return MSR3D_EINVAL;
+  if (B == 0) return 0;
+  if (!x0 || !pos || !cos_td || !sin_td || !al16(x0) || !al16(x1) || !al16(cos_td) || !al16(sin_td)) return MSR3D_EINVAL;
+  const long long n = (long long)B * T * H * (D / 16);
+  rope_positions_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(n, H, D, (u16 *)x0, (u16 *)x1, pos,
+                                                                                    table_rows, cos_td, sin_td);
+  return (int)hipGetLastError();
+}
+
+int msr3d_rope_kv_append(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,
+                         const int *len, const float *cos_td, const float *sin_td, int table_rows, void *k_cache,
+                         void *v_cache, msr3d_stream_t stream) {
+  if (N < 0 || H <= 0 || D <= 0 || (D % 16) || Tmax <= 0 || table_rows <= 0 || ld < H * D || (ld % 8)) return MSR3D_EINVAL;
+  if (N == 0) return 0;
+  if (!q || !k || !v || !pos || !len || !cos_td || !sin_td || !k_cache || !v_cache) return MSR3D_EINVAL;
+  if (!al16(q) || !al16(k) || !al16(v) || !al16(cos_td) || !al16(sin_td) || !al16(k_cache) || !al16(v_cache))
+    return MSR3D_EINVAL;
+  const long long n = (long long)N * H * (D / 16);
+  if (n > 0x7fffffffLL) return MSR3D_EINVAL;
+  rope_kv_append_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      (int)n, H, D, Tmax, (u16 *)q, (const u16 *)k, (const u16 *)v, ld, pos, len, table_rows, cos_td, sin_td, (u16 *)k_cache,
+      (u16 *)v_cache);
+  return (int)hipGetLastError();
+}
+
+int msr3d_attn_decode_splits(int N, int H) {
+  if (N <= 0 || H <= 0) return 1;
+  const long long wg = (long long)N * H;
+  if (wg >= 256) return 1;
+  const int s = (int)((512 + wg - 1) / wg);
+  return s > MSR3D_ATTN_DECODE_MAX_SPLITS ? MSR3D_ATTN_DECODE_MAX_SPLITS : s;
+}
+
+int msr3d_attn_decode(int N, int Tmax, int H, int D, const void *q, int ldq, const void *k_cache, const void *v_cache,
+                      const int *len, int len_add, const unsigned char *key_keep, float scale, void *out, int ldo,
+                      float *workspace, long long workspace_floats, msr3d_stream_t stream) {
+  if (N < 0 || Tmax <= 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) || ldo < H * D) return MSR3D_EINVAL;
+  if (N == 0) return 0;
+  if (N > 65535 || !q || !k_cache || !v_cache || !len || !out || !al16(q) || !al16(k_cache) || !al16(v_cache))
+    return MSR3D_EINVAL;
+  int S = workspace ? msr3d_attn_decode_splits(N, H) : 1;
+  if (S > 1 && workspace_floats < (long long)N * H * S * (D + 2)) return MSR3D_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(H, N, S);
+  float *part = S > 1 ? workspace : nullptr;
+  if (D == 128)
+    attn_decode_kernel<128><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, (const u16 *)k_cache, (const u16 *)v_cache, len,
+                                                  len_add, key_keep, sl2, (u16 *)out, ldo, part);
+  else
+    attn_decode_kernel<64><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, (const u16 *)k_cache, (const u16 *)v_cache, len,
+                                                 len_add, key_keep, sl2, (u16 *)out, ldo, part);
+  if (S > 1) {
+    if (D == 128) attn_merge_kernel<128><<<dim3(H, N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
+    else attn_merge_kernel<64><<<dim3(H, N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
+  }
+  return (int)hipGetLastError();
+}
+
+int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src, void *dst, const int *beam_idx,
+                     const int *len, msr3d_stream_t stream) {
+  if (planes < 0 || N < 0 || Tmax <= 0 || row_elems <= 0 || (row_elems % 8)) return MSR3D_EINVAL;
+  if (planes == 0 || N == 0) return 0;
+  if (planes > 65535 || N > 65535 || !src || !dst || src == dst || !beam_idx || !len || !al16(src) || !al16(dst))
+    return MSR3D_EINVAL;
+  const long long per_row = (long long)Tmax * (row_elems / 8);       // 16-byte pieces of a full row; a block takes ~8 per thread
+  long long gx = (per_row + 2047) / 2048;
+  gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+  kv_reorder_kernel<<<dim3((unsigned)gx, N, planes), 256, 0, (hipStream_t)stream>>>(N, Tmax, row_elems / 8, (const uint4 *)src,
+                                                                               (uint4 *)dst, beam_idx, len);
+  return (int)hipGetLastError();
+}
+
+int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,
+                        const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
+                        int order, int k, float *out_val, int *out_tok, msr3d_stream_t stream) {
+  if (N < 0 || V <= 0 || V > MSR3D_DECODE_SELECT_MAX_V || ldl < V || k <= 0 || k > V || k > MSR3D_DECODE_SELECT_MAX_K ||
+      (order != 0 && order != 1) || !(repetition_penalty > 0.f) || ld_prev < 0)
+    return MSR3D_EINVAL;
+  if (N == 0) return 0;
+  if (!logits || !out_val || !out_tok || (n_prev && !prev_tokens)) return MSR3D_EINVAL;
+  if ((size_t)V * sizeof(float) > 48 * 1024) {
+    // more dynamic LDS than the default limit: 160 KB a workgroup on this part, 160 000 bytes at the largest V
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(decode_select_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, MSR3D_DECODE_SELECT_MAX_V * 4);
+    if (e != hipSuccess) return (int)e;
+  }
+  decode_select_kernel<<<N, 256, (size_t)V * sizeof(float), (hipStream_t)stream>>>(
+      V, (const u16 *)logits, ldl, prev_tokens, ld_prev, n_prev, ld_prev, repetition_penalty, min_length, eos_id, beam_score,
+      order, k, out_val, out_tok);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

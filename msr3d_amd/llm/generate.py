@@ -1,0 +1,399 @@
+"""`generate` for the LoRA-Llama stack: greedy and beam search over a key / value cache, one new token per step on the
+decode kernels of csrc/llm_decode.hip (what transformers' `LlamaForCausalLM.generate(inputs_embeds=..., attention_mask=...,
+num_beams=..., repetition_penalty=..., length_penalty=...)` computes; the reference's MSR3D.generate calls exactly that).
+
+Three pieces:
+
+* `KVCache`        the buffers of one call: K / V (layers, 2, rows, t_max, heads, head_dim) bf16, token-major like the
+                   projections' own output, twice when beams are reordered (ping-pong), and per row `len` (cache slots in
+                   use), `pos` (the next rotary position = number of unmasked tokens so far) and `keep` (key padding).
+                   Allocated once per call, never resized.
+* `CachedDecoder`  the engine: `prefill` runs the existing layer forward kernels over the padded prompt (positions =
+                   cumsum(mask) - 1, clamped at 0: what transformers' generate feeds Llama when it is given a mask) and
+                   writes every layer's K / V into the cache; `step` runs one token per live row: per layer RMSNorm,
+                   q | k | v as ONE skinny launch, rotation + cache append, decode attention, o, RMSNorm, gate | up with the
+                   SwiGLU epilogue, down; then the final norm and the head.  No host synchronisation inside `step`: lengths
+                   and positions live in device memory.
+* `search`         greedy / beam search with transformers' semantics, written against the engine interface alone
+                   (`reserve`, `prefill`, `expand`, `step`, and optionally `select`), so it runs on the CPU with any
+                   engine: that is how its logic is checked exactly against transformers.
+
+`max_length` counts GENERATED tokens (the prompt travels as embeddings and has no ids).  GPU only for the engine."""
+import ctypes
+import math
+
+import torch
+
+from .. import _lib
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _call(name, *args):
+    rc = getattr(_lib.load(), name)(*args)
+    _lib.check(rc, name)
+
+
+# ------------------------------------------------------------------------------------------------ selection, in torch
+def torch_select(logits, prev, repetition_penalty, min_length, eos_id, beam_score, order, k):
+    """The fp32 statement of msr3d_decode_select, device-agnostic: per row the top k (value, token) of
+    order 0: log_softmax(processors(logits)) + beam_score;  order 1: processors(log_softmax(logits)) + beam_score,
+    processors = transformers' RepetitionPenaltyLogitsProcessor over prev (N, n_prev) then MinLengthLogitsProcessor."""
+    x = logits.float()
+
+    def processors(s):
+        if repetition_penalty != 1.0 and prev.shape[1] > 0:
+            g = torch.gather(s, 1, prev)
+            g = torch.where(g < 0, g * repetition_penalty, g / repetition_penalty)
+            s = s.scatter(1, prev, g)
+        if prev.shape[1] < min_length and eos_id is not None and eos_id >= 0:
+            s = s.clone()
+            s[:, eos_id] = -math.inf
+        return s
+
+    if order == 0:
+        s = torch.log_softmax(processors(x), dim=-1)
+    else:
+        s = processors(torch.log_softmax(x, dim=-1))
+    if beam_score is not None:
+        s = s + beam_score.float()[:, None]
+    val, tok = torch.topk(s, k, dim=-1)
+    return val, tok
+
+
+# ----------------------------------------------------------------------------------------------------------- search
+@torch.no_grad()
+def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=2, pad_id=2, num_beams=1, max_length=256,
+           min_length=1, repetition_penalty=1.0, length_penalty=1.0):
+    """-> (B, <= max_length) int64: the generated tokens (the prompt is not part of the result).
+    engine: `prefill(inputs_embeds (B, T, H), attention_mask (B, T)) -> (B, V)` logits of the last position,
+    `expand(beams)` (every prompt row becomes `beams` adjacent rows), `step(embeds (N, H), beam_idx=None) -> (N, V)`
+    (beam_idx (N,): row n continues the cache of row beam_idx[n]); optionally `reserve(rows_per_prompt, new_tokens)`
+    called first and `select(...)` with torch_select's signature.  embed_fn: token ids (N,) -> embeddings (N, H).
+    bos_id: its embedding and a mask column of ones are appended to the prompt first (the reference's generate does that
+    itself).  Semantics are transformers' (`do_sample=False`, `early_stopping=False`): greedy rows that have emitted eos
+    go on as pad_id; beam search keeps 2 x beams candidates a step, scores finished hypotheses
+    sum_logprobs / len ** length_penalty and stops when no running beam can beat the worst kept hypothesis.
+    One host synchronisation per step (the done test), as transformers has."""
+    if num_beams < 1 or max_length < 1:
+        raise ValueError("num_beams >= 1 and max_length >= 1")
+    x, mask = inputs_embeds, attention_mask
+    dev = x.device
+    if bos_id is not None:
+        bos = embed_fn(torch.full((x.shape[0],), int(bos_id), dtype=torch.int64, device=dev)).to(x.dtype)
+        x = torch.cat([x, bos[:, None]], 1)
+        mask = torch.cat([mask, torch.ones_like(mask[:, :1])], 1)
+    B, nb, L = x.shape[0], int(num_beams), int(max_length)
+    if hasattr(engine, "reserve"):
+        engine.reserve(nb, L)
+    select = getattr(engine, "select", torch_select)
+    logits = engine.prefill(x, mask)
+    engine.expand(nb)
+    eos = -1 if eos_id is None else int(eos_id)
+
+    if nb == 1:
+        seq = torch.full((B, L), int(pad_id), dtype=torch.int64, device=dev)
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        for cur in range(L):
+            _, tok = select(logits, seq[:, :cur], repetition_penalty, min_length, eos, None, 0, 1)
+            nxt = torch.where(unfinished, tok[:, 0].long(), torch.full_like(tok[:, 0].long(), int(pad_id)))
+            seq[:, cur] = nxt
+            unfinished = unfinished & (nxt != eos)
+            if cur + 1 >= L or not bool(unfinished.any()):
+                break
+            logits = engine.step(embed_fn(nxt))
+        return seq[:, :cur + 1]
+
+    K2 = 2 * nb
+    f32 = torch.float32
+    run_scores = torch.zeros((B, nb), dtype=f32, device=dev)
+    run_scores[:, 1:] = -1.0e9
+    run_seq = torch.full((B, nb, L), int(pad_id), dtype=torch.int64, device=dev)
+    fin_seq = run_seq.clone()
+    fin_scores = torch.full((B, nb), -1.0e9, dtype=f32, device=dev)
+    fin_len = torch.zeros((B, nb), dtype=torch.int64, device=dev)
+    is_fin = torch.zeros((B, nb), dtype=torch.bool, device=dev)
+    heur = torch.ones((B, 1), dtype=torch.bool, device=dev)
+    top_mask = torch.arange(K2, device=dev) < nb
+    offs = (torch.arange(B, device=dev) * nb)[:, None]
+    logits = logits.repeat_interleave(nb, 0)
+
+    def take(t, i):                       # t (B, n, ...), i (B, m) -> (B, m, ...)
+        return torch.gather(t, 1, i.view(*i.shape, *([1] * (t.dim() - 2))).expand(*i.shape, *t.shape[2:]))
+
+    for cur in range(L):
+        val, tok = select(logits, run_seq.view(B * nb, L)[:, :cur], repetition_penalty, min_length, eos,
+                          run_scores.view(-1), 1, K2)
+        top_val, top_i = torch.topk(val.view(B, nb * K2).float(), K2, dim=1)
+        src_beam = top_i // K2
+        tok_k = torch.gather(tok.view(B, nb * K2).long(), 1, top_i)
+        top_seq = take(run_seq, src_beam)
+        top_seq[:, :, cur] = tok_k
+        hits = tok_k == eos
+        if cur + 1 >= L:
+            hits = torch.ones_like(hits)
+        # the running beams of the next step: the best candidates that did not just end
+        run_lp = top_val + hits.to(f32) * -1.0e9
+        nxt_i = torch.topk(run_lp, nb, dim=1)[1]
+        run_seq, run_scores, beam_sel = take(top_seq, nxt_i), take(run_lp, nxt_i), take(src_beam, nxt_i)
+        # finished hypotheses: only a candidate among the first `beams` may be kept
+        did = hits & top_mask[None]
+        fl = top_val / ((cur + 1) ** length_penalty)
+        fl = fl + (~heur).to(f32) * -1.0e9
+        fl = fl + (~did).to(f32) * -1.0e9
+        m_scores = torch.cat([fin_scores, fl], 1)
+        mi = torch.topk(m_scores, nb, dim=1)[1]
+        fin_seq = take(torch.cat([fin_seq, top_seq], 1), mi)
+        fin_len = take(torch.cat([fin_len, torch.full_like(tok_k, cur + 1)], 1), mi)
+        is_fin = take(torch.cat([is_fin, did], 1), mi)
+        fin_scores = take(m_scores, mi)
+        # can a running beam still beat the worst kept hypothesis?  (early_stopping = False: judged at the current length)
+        best_running = run_scores[:, :1] / ((cur + 1) ** length_penalty)
+        worst_fin = torch.where(is_fin, fin_scores.min(1, keepdim=True)[0], torch.full_like(fin_scores, -1.0e9))
+        heur = heur & (best_running > worst_fin).any(-1, keepdim=True)
+        if not bool(heur.any() & ~hits.all()):
+            break
+        logits = engine.step(embed_fn(run_seq[:, :, cur].reshape(-1)), (beam_sel + offs).reshape(-1))
+    return fin_seq[:, 0, :int(fin_len[:, 0].max())]
+
+
+# ------------------------------------------------------------------------------------------------------------ cache
+class KVCache:
+    """kv[side] (layers, 2, rows, t_max, heads, head_dim) bf16, side = `cur` is the live one (two sides only with
+    `pingpong`: msr3d_kv_reorder gathers from one into the other); len, pos (rows) int32; keep (rows, t_max) uint8."""
+
+    def __init__(self, layers, rows, t_max, heads, head_dim, device, pingpong=False):
+        self.layers, self.rows, self.t_max, self.heads, self.head_dim = layers, rows, t_max, heads, head_dim
+        sides = 2 if pingpong else 1
+        self.kv = [torch.zeros((layers, 2, rows, t_max, heads, head_dim), dtype=torch.bfloat16, device=device)
+                   for _ in range(sides)]
+        self.cur = 0
+        mk = lambda *s, dt: [torch.zeros(s, dtype=dt, device=device) for _ in range(sides)]     # noqa: E731
+        self._len, self._pos = mk(rows, dt=torch.int32), mk(rows, dt=torch.int32)
+        self._keep = [torch.ones((rows, t_max), dtype=torch.uint8, device=device) for _ in range(sides)]
+        splits = _lib.load().msr3d_attn_decode_splits(rows, heads)
+        self.workspace = (torch.empty(rows * heads * splits * (head_dim + 2), dtype=torch.float32, device=device)
+                          if splits > 1 else None)
+
+    len = property(lambda self: self._len[self.cur])
+    pos = property(lambda self: self._pos[self.cur])
+    keep = property(lambda self: self._keep[self.cur])
+
+    def k(self, layer):
+        return self.kv[self.cur][layer, 0]
+
+    def v(self, layer):
+        return self.kv[self.cur][layer, 1]
+
+    def reorder(self, beam_idx):
+        """Row n continues row beam_idx[n]: one launch for every layer's K and V, into the other side."""
+        if len(self.kv) < 2:
+            raise RuntimeError("KVCache: allocated without the second side (pingpong=True) a reorder needs")
+        idx = beam_idx.to(torch.int32).contiguous()
+        src, dst = self.kv[self.cur], self.kv[1 - self.cur]
+        dev = src.device
+        with torch.cuda.device(dev):
+            _call("msr3d_kv_reorder", self.layers * 2, self.rows, self.t_max, self.heads * self.head_dim, _p(src), _p(dst),
+                  _p(idx), _p(self.len), _lib.current_stream_ptr(dev))
+        il = idx.long()
+        for pair in (self._len, self._pos, self._keep):
+            torch.index_select(pair[self.cur], 0, il, out=pair[1 - self.cur])
+        self.cur = 1 - self.cur
+
+
+# ----------------------------------------------------------------------------------------------------------- engine
+class CachedDecoder:
+    """The decoding engine of a LoRALlamaStack (see the module docstring).  bf16 base weights only."""
+
+    def __init__(self, stack):
+        from .lora import LoRALinear
+        self.stack = stack
+        self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
+        if any(m.base == "fp8" for m in self.mods):
+            raise NotImplementedError("CachedDecoder: base='fp8' stacks are not supported (the decode products read the bf16 "
+                                      "weights; e4m3 decoding is not implemented)")
+        if not stack.layers:
+            raise ValueError("CachedDecoder: a stack without layers")
+        l0 = stack.layers[0]
+        self.H, self.D, self.hidden = l0.num_heads, l0.head_dim, l0.hidden_size
+        self.cache, self._plan, self._tables = None, (1, 256), None
+
+    def reserve(self, rows_per_prompt, new_tokens):
+        self._plan = (int(rows_per_prompt), int(new_tokens))
+
+    # -- prefill ---------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prefill(self, inputs_embeds, attention_mask):
+        from .decoder import _AttentionFn, _RMSNormFn, _SwiGLUFn, rope_tables
+        from .lora import refresh_shadows
+        st = self.stack
+        if not inputs_embeds.is_cuda:
+            raise RuntimeError("CachedDecoder runs on the GPU only (no CPU fallback)")
+        x = inputs_embeds.to(torch.bfloat16)
+        B, T, Hd = x.shape
+        H, D, dev = self.H, self.D, x.device
+        beams, new_tokens = self._plan
+        if B * beams > 32:
+            raise ValueError("CachedDecoder: at most 32 live rows (batch x beams)")
+        mask = attention_mask.to(dev).bool()
+        Tp = -(-T // 64) * 64
+        if Tp != T:
+            x = torch.cat([x, torch.zeros((B, Tp - T, Hd), dtype=x.dtype, device=dev)], 1)
+            mask = torch.cat([mask, torch.zeros((B, Tp - T), dtype=torch.bool, device=dev)], 1)
+        x = x.contiguous()
+        keep = mask.to(torch.uint8).contiguous()
+        pos = (mask.long().cumsum(-1) - 1).clamp_min(0).to(torch.int32).contiguous()
+        t_max = T + new_tokens
+        cache = self.cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1)
+        rows = max(t_max, Tp)
+        cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
+        self._tables = (cos, sin, rows)
+        refresh_shadows(self.mods, False)
+        first = slice(0, B * beams, beams)                     # a prompt's first row; expand() fills the others
+        delta, last = None, len(st.layers) - 1
+        for i, layer in enumerate(st.layers):
+            a, m = layer.self_attn, layer.mlp
+            x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
+            q, k, v = a["q_proj"].forward2d(h), a["k_proj"].forward2d(h), a["v_proj"].forward2d(h)
+            with torch.cuda.device(dev):
+                _call("msr3d_rope_positions", B, Tp, H, D, _p(q), _p(k), _p(pos), _p(cos), _p(sin), rows,
+                      _lib.current_stream_ptr(dev))
+            q, k, v = q.view(B, Tp, H, D), k.view(B, Tp, H, D), v.view(B, Tp, H, D)
+            cache.k(i)[first, :T] = k[:, :T]
+            cache.v(i)[first, :T] = v[:, :T]
+            o = a["o_proj"](_AttentionFn.apply(q, k, v, keep))
+            if i == last:                                      # only the last position's logits are wanted
+                x0, o = x0[:, T - 1:T].contiguous(), o[:, T - 1:T].contiguous()
+            x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
+            y = m["down_proj"](_SwiGLUFn.apply(m["gate_proj"](h2), m["up_proj"](h2)))
+            x, delta = x1, y
+        _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
+        cache.len[first] = T
+        cache.pos[first] = mask.sum(-1).to(torch.int32)
+        cache.keep[first, :T] = keep[:, :T]
+        return st.lm_head(h)[:, 0]
+
+    def expand(self, beams):
+        c = self.cache
+        if c is None or beams != self._plan[0]:
+            raise RuntimeError("CachedDecoder.expand: call reserve(beams, new_tokens) and prefill first")
+        if beams == 1:
+            return
+        B, T = c.rows // beams, int(c.t_max - self._plan[1])
+        kv = c.kv[c.cur].view(c.layers, 2, B, beams, c.t_max, c.heads, c.head_dim)
+        kv[:, :, :, 1:, :T] = kv[:, :, :, :1, :T]
+        for t in (c.len, c.pos, c.keep):
+            g = t.view(B, beams, *t.shape[1:])
+            g[:, 1:] = g[:, :1]
+
+    # -- one token ------------------------------------------------------------------------------------------------
+    def _products(self, h, mods, swiglu=False):
+        """The projections `mods` of the same activations h (M, K) -> list of (M, N) bf16 (one tensor with swiglu):
+        members of one input group share the low-rank activation and ONE launch."""
+        from .lora import PAD_R, _skinny
+        M, K = h.shape
+        dev = h.device
+        outs, calls = [None] * len(mods), {}
+        for j, m in enumerate(mods):
+            m._sync_weight_t()
+            calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
+        if swiglu and len(calls) != 1:
+            # gate and up without a shared low-rank activation (modules moved to the device after construction leave
+            # their input group): two products and the stand-alone SwiGLU launch
+            gate, up = self._products(h, mods)
+            act = torch.empty_like(gate)
+            with torch.cuda.device(dev):
+                _call("msr3d_swiglu_fwd", gate.numel(), _p(gate), _p(up), _p(act), _lib.current_stream_ptr(dev))
+            return [act]
+        for js in calls.values():
+            m0 = mods[js[0]]
+            a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
+            u = torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev)
+            _skinny(M, a_op.shape[0], K, h, a_op, u, PAD_R, m0.scaling, dev)
+            jobs = (_lib.SkinnyJob * len(js))()
+            for n, j in enumerate(js):
+                m = mods[j]
+                b2 = m._shadows(forward=True)[1]
+                if not (swiglu and n == 1):
+                    outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
+                jobs[n] = _lib.SkinnyJob(m.weight.data_ptr(), K, b2.data_ptr(), PAD_R,
+                                         outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
+            with torch.cuda.device(dev):
+                _call("msr3d_bf16_skinny_lowrank", M, K, PAD_R, _p(h), K, _p(u), PAD_R, len(js), jobs, int(swiglu),
+                      _lib.current_stream_ptr(dev))
+        return outs
+
+    @torch.no_grad()
+    def step(self, embeds, beam_idx=None):
+        """embeds (N, hidden): the embeddings of the tokens just chosen -> logits (N, V) bf16 of the next position."""
+        from .decoder import _RMSNormFn
+        st, c = self.stack, self.cache
+        if c is None:
+            raise RuntimeError("CachedDecoder.step before prefill")
+        x = embeds.to(torch.bfloat16).contiguous()
+        N, dev = x.shape[0], x.device
+        if N != c.rows or x.shape[1] != self.hidden:
+            raise ValueError("CachedDecoder.step: embeds must be (rows, hidden)")
+        if beam_idx is not None:
+            c.reorder(beam_idx)
+        H, D, HD = self.H, self.D, self.H * self.D
+        cos, sin, rows = self._tables
+        scale = 1.0 / math.sqrt(D)
+        ws = c.workspace
+        delta = None
+        for i, layer in enumerate(st.layers):
+            a, m = layer.self_attn, layer.mlp
+            x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
+            q, k, v = self._products(h, [a["q_proj"], a["k_proj"], a["v_proj"]])
+            ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=dev)
+            with torch.cuda.device(dev):
+                s = _lib.current_stream_ptr(dev)
+                _call("msr3d_rope_kv_append", N, H, D, c.t_max, _p(q), _p(k), _p(v), HD, _p(c.pos), _p(c.len), _p(cos),
+                      _p(sin), rows, _p(c.k(i)), _p(c.v(i)), s)
+                _call("msr3d_attn_decode", N, c.t_max, H, D, _p(q), HD, _p(c.k(i)), _p(c.v(i)), _p(c.len), 1, _p(c.keep),
+                      ctypes.c_float(scale), _p(ctx), HD, _p(ws), ws.numel() if ws is not None else 0, s)
+            o, = self._products(ctx, [a["o_proj"]])
+            x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
+            act = self._products(h2, [m["gate_proj"], m["up_proj"]], swiglu=True)[0]
+            y, = self._products(act, [m["down_proj"]])
+            x, delta = x1, y
+        _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
+        head = st.lm_head
+        head._sync()
+        logits = torch.empty((N, head.out_features), dtype=torch.bfloat16, device=dev)
+        job = (_lib.SkinnyJob * 1)(_lib.SkinnyJob(head.weight.data_ptr(), head.in_features, 0, 0, logits.data_ptr(),
+                                                  head.out_features, head.out_features))
+        with torch.cuda.device(dev):
+            _call("msr3d_bf16_skinny_lowrank", N, head.in_features, 0, _p(h), head.in_features, _p(None), 0, 1, job, 0,
+                  _lib.current_stream_ptr(dev))
+        c.len.add_(1)
+        c.pos.add_(1)
+        return logits
+
+    def select(self, logits, prev, repetition_penalty, min_length, eos_id, beam_score, order, k):
+        """msr3d_decode_select on the step's logits; `prev` (N, n_prev) int64: the rows' generated tokens."""
+        if not logits.is_cuda:
+            raise RuntimeError("CachedDecoder.select runs on the GPU only")
+        lg = logits.to(torch.bfloat16).contiguous()
+        N, V = lg.shape
+        dev = lg.device
+        has_prev = prev.shape[1] > 0                      # (no token yet: NULL, which the entry reads as "none")
+        prev = prev.contiguous() if has_prev else None
+        n_prev = torch.full((N,), prev.shape[1], dtype=torch.int32, device=dev) if has_prev else None
+        val = torch.empty((N, k), dtype=torch.float32, device=dev)
+        tok = torch.empty((N, k), dtype=torch.int32, device=dev)
+        bs = None if beam_score is None else beam_score.float().contiguous()
+        with torch.cuda.device(dev):
+            _call("msr3d_decode_select", N, V, _p(lg), V, _p(prev), prev.shape[1] if has_prev else 0, _p(n_prev),
+                  ctypes.c_float(repetition_penalty), int(min_length), int(-1 if eos_id is None else eos_id), _p(bs),
+                  int(order), int(k), _p(val), _p(tok), _lib.current_stream_ptr(dev))
+        return val, tok
+
+
+@torch.no_grad()
+def generate(stack, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
+    """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings)."""
+    embed_fn = embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
+    return search(CachedDecoder(stack), embed_fn, inputs_embeds, attention_mask, **search_kwargs)

@@ -152,6 +152,14 @@ class LoRALlamaStack(nn.Module):
                 m._fresh_in_capture = False
         return self.lm_head(h)
 
+    def generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
+        """Greedy / beam search from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py) ->
+        (B, <= max_length) int64 generated tokens.  embed_tokens: the (V, hidden) embedding table (or a callable
+        ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams, max_length (GENERATED tokens), min_length,
+        repetition_penalty, length_penalty."""
+        from .generate import generate
+        return generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs)
+
     def forward(self, inputs_embeds, attention_mask=None, targets=None, supervised_from=None):
         """-> logits (B, T, V) bf16, or with `targets` (B, T) int64 (negative = not supervised) the per-sequence mean
         cross-entropy (B,) of msr3d.py:426-441.

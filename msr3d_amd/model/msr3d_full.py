@@ -9,8 +9,10 @@
                  LoRALlamaStack (n decoder layers + norm + head) + seq-CE     ─► loss (B,)
 
 What is NOT here (out of SURVEY §8's scope): tokenizer and prompt assembly (the step takes
-token ids), the 2D image branch (`image_encoder`, `llm_proj_img`: one placeholder token per sequence), CLIP fusion,
-`generate`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
+token ids), the 2D image branch (`image_encoder`, `llm_proj_img`: one placeholder token per sequence), CLIP fusion, and of the reference's `generate`
+everything but greedy / beam search: nucleus sampling, `num_captions > 1`, `pred_action`, `predict_answers`.
+`MSR3DFullStep.generate` is the reference's evaluation path (msr3d.py:445-524): prompt embeddings + scene tokens + one bos
+embedding -> KV-cached beam search (msr3d_amd/llm/generate.py) -> `output_tokens`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
 under `llm_model.*` (msr3d_amd/llm/checkpoint.py maps Hugging Face / peft keys onto it).
 
 GPU only beyond the prompter: the language-model kernels have no CPU fallback."""
@@ -18,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from .build import MODEL_REGISTRY
-from .scene_embeds import SCENE_SP_TOKEN, MSR3DHotPath, scatter_scene_embeds_train_
+from .scene_embeds import SCENE_SP_TOKEN, MSR3DHotPath, scatter_scene_embeds_, scatter_scene_embeds_train_
 
 
 def build_targets(T_in, output_ids, output_mask):
@@ -85,4 +87,37 @@ class MSR3DFullStep(MSR3DHotPath):
         emb, am, targets = self.embed_inputs(d, d["scene_embeds"], d["obj_masks"])
         # (targets are -100 over the whole prompt by construction: the head and the loss run over the answer span only)
         d["loss"] = self.llm_model(emb, attention_mask=am, targets=targets, supervised_from=data_dict["input_ids"].shape[1])
+        return d
+
+    @torch.no_grad()
+    def generate(self, data_dict, num_beams=5, max_length=256, min_length=1, repetition_penalty=3.0, length_penalty=1.0,
+                 max_out_len=256, bos_id=1, eos_id=2):
+        """The reference's MSR3D.generate with `use_nucleus_sampling=False`: hot path -> prompt embeddings with the scene
+        tokens written in and the object mask at their positions (prompt only, no answer) -> one bos embedding and a mask
+        column of ones appended -> beam search over the key / value cache (`max_length` counts generated tokens) ->
+        id 0 mapped to 2 -> padded with 2 to `max_out_len` -> data_dict['output_tokens'] (B, max_out_len) int64.
+        The prompt may have any length (the engine pads it to the attention kernel's multiple of 64 itself)."""
+        if not data_dict["input_ids"].is_cuda:
+            raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
+        if max_length > max_out_len:
+            raise ValueError("max_length (generated tokens) must not exceed max_out_len")
+        # the hot path with ordered reductions (hipops.set_deterministic: by default its split-K partial sums meet by float
+        # atomics, 5e-6 apart from call to call -- enough to flip a bf16 scene token and, now and then, a beam): evaluation
+        # output is the same tokens call after call; decoding itself has no atomics
+        from .. import hipops
+        was = hipops.set_deterministic(True)
+        try:
+            d = MSR3DHotPath.forward(self, data_dict)
+        finally:
+            hipops.set_deterministic(was)
+        ids = data_dict["input_ids"].contiguous()
+        am = data_dict["attention_mask"].to(torch.int64).contiguous().clone()
+        emb = F.embedding(ids, self.embed_tokens).contiguous()
+        scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
+        out = self.llm_model.generate(emb, am, self.embed_tokens, bos_id=bos_id, eos_id=eos_id, pad_id=eos_id,
+                                      num_beams=num_beams, max_length=max_length, min_length=min_length,
+                                      repetition_penalty=repetition_penalty, length_penalty=length_penalty)
+        out = torch.where(out == 0, torch.full_like(out, 2), out)
+        pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
+        d["output_tokens"] = torch.cat([out, pad], 1)
         return d

@@ -1,0 +1,111 @@
+"""Times KV-cached decoding (msr3d_amd/llm/generate.py) at Vicuna-7B layer shapes with random weights: the prefill and one
+decode step at N live rows x cache length, against (a) the only way to get a token without a cache --
+`LoRALlamaStack.logits(..., from_position=T-1)` on the 64-padded prefix, same process, alternating -- and (b) the
+streaming floor: bytes of weights + cache a step must read / 6.29 TB/s (the rate a streaming copy reaches on an MI355X).
+Device events around every repeat (warm-up first, >= 20 repeats): median and spread.  Prints one JSON line.
+
+    python tools/bench_generate.py [--layers 4] [--repeats 20] [--rows 1,5,20] [--lengths 128,320,576]
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --profile 5x320      # per-kernel, own run
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from msr3d_amd.llm import LoRALlamaStack  # noqa: E402
+from msr3d_amd.llm.generate import CachedDecoder  # noqa: E402
+
+HIDDEN, HEADS, INTER, VOCAB = 4096, 32, 11008, 32000
+COPY_RATE = 6.29e12
+
+
+def build(layers):
+    net = LoRALlamaStack(layers, HIDDEN, HEADS, INTER, VOCAB, device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    with torch.no_grad():
+        for n, b in net.named_buffers():
+            if n.endswith("weight") and b.dim() == 2:
+                b.copy_(torch.randn(b.shape, generator=gen, device="cuda") * b.shape[1] ** -0.5)
+        for p in net.lora_parameters():
+            if p.shape[0] != 16:                      # lora_B: zeros at init; give it values so the term is live
+                p.copy_(torch.randn(p.shape, generator=gen, device="cuda") * 0.02)
+    return net
+
+
+def timed(fn, repeats, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3)
+    ts.sort()
+    return {"median_us": round(statistics.median(ts), 1), "min_us": round(ts[0], 1), "max_us": round(ts[-1], 1)}
+
+
+def step_bytes(layers, rows, length):
+    per_layer = 2 * (4 * HIDDEN * HIDDEN + 3 * HIDDEN * INTER)
+    cache = 2 * 2 * rows * length * HIDDEN
+    return layers * (per_layer + cache) + 2 * HIDDEN * VOCAB
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--rows", default="1,5,20")
+    ap.add_argument("--lengths", default="128,320,576")
+    ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_generate needs a GPU"
+    net = build(args.layers)
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    grid = [(int(r), int(t)) for r in args.rows.split(",") for t in args.lengths.split(",")]
+    if args.profile:
+        grid = [tuple(int(v) for v in args.profile.split("x"))]
+    out = {"bench": "generate", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
+           "heads": HEADS, "inter": INTER, "vocab": VOCAB, "repeats": args.repeats, "copy_rate_TBps": COPY_RATE / 1e12,
+           "cells": []}
+    for rows, length in grid:
+        x = (torch.randn(1, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(1, length, dtype=torch.int64, device="cuda")
+        eng = CachedDecoder(net)
+        eng.reserve(rows, args.repeats + 8)
+        prefill = None
+        if not args.profile:
+            prefill = timed(lambda: eng.prefill(x, mask), max(5, args.repeats // 4), warmup=2)
+        eng.prefill(x, mask)
+        eng.expand(rows)
+        tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+        cached = timed(lambda: eng.step(tok), args.repeats)
+        cell = {"rows": rows, "length": length, "prefill_1row": prefill, "step": cached}
+        floor = step_bytes(args.layers, rows, length) / COPY_RATE * 1e6
+        cell["floor_us"] = round(floor, 1)
+        cell["floor_fraction"] = round(floor / cached["median_us"], 3)
+        if not args.profile:
+            # the parent's way: a full forward over the 64-padded prefix (length + 1 tokens), logits of the last one only
+            Tp = -(-(length + 1) // 64) * 64
+            xf = (torch.randn(rows, Tp, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+            mf = torch.ones(rows, Tp, dtype=torch.uint8, device="cuda")
+            mf[:, length + 1:] = 0
+            with torch.no_grad():
+                full = timed(lambda: net.logits(xf, mf, from_position=length), max(5, args.repeats // 2), warmup=2)
+            cell["full_forward"] = full
+            cell["speedup"] = round(full["median_us"] / cached["median_us"], 2)
+        out["cells"].append(cell)
+        del eng
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
