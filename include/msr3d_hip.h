@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 30
+#define MSR3D_ABI_VERSION 31
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1157,6 +1157,27 @@ int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long lo
                         const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
                         int order, int k, float *out_val, int *out_tok, msr3d_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Prefix-shared attention (csrc/llm_attn.hip; CachedDecoder.score, closed-set answer ranking): C candidate suffixes of
+ * S tokens per prompt attend to ONE cached prefix of that prompt.  q, k, v (B, C, S, H, D) bf16 with row stride ld,
+ * RoPE applied; k_cache, v_cache (B, Tmax, H, D) bf16, contiguous (KVCache rows); len (B) int32 in DEVICE memory,
+ * clamped to 0 .. Tmax before it forms an address; prefix_keep (B, Tmax) bytes; suffix_keep (B C, S) bytes or NULL
+ * (every slot kept).  Query (b, c, j) sees the prefix keys t < min(len[b], Tmax) of cache row b with
+ * prefix_keep[b][t] != 0 and the suffix keys (b, c, j'), j' <= j, with suffix_keep != 0; no other candidate's keys.
+ * out (B, C, S, H, D) bf16 with row stride ldo = softmax(scale q k^T) v per head; a row with no visible key gives 0.
+ * Cache slots >= len are never read into a product (NaN bit patterns there are harmless); no row >= Tmax is read.
+ * D = 64 or 128; S = 16, 32 or 64 (pad the suffix with masked slots); B, C, len, Tmax arbitrary (B = 0 or C = 0: no-op;
+ * Tmax = 0: the cache pointers may be NULL).  ld, ldo % 8 == 0; q, k, v and the caches 16-byte aligned.
+ * Forward only, no atomics, one owner per output row: bit-reproducible.
+ * msr3d_attn_prefix_order: the workgroup numbering, a matter of speed alone (the same bits either way).  0 (default):
+ *   the 64-row tiles of one (prompt, head) are 8 workgroups apart, so that under round-robin dispatch over the eight
+ *   XCDs they meet in one L2 and the prefix is fetched from memory once; 1: adjacent (for measuring the difference).
+ *   order = 0 / 1 selects, -1 only queries; returns the order in force, MSR3D_EINVAL for another value.
+ * ------------------------------------------------------------------------- */
+int msr3d_attn_prefix_order(int order);
+int msr3d_attn_prefix_fwd(int B, int C, int S, int Tmax, int H, int D, const void *q, const void *k, const void *v, int ld,
+                          const void *k_cache, const void *v_cache, const int *len, const unsigned char *prefix_keep,
+                          const unsigned char *suffix_keep, float scale, void *out, int ldo, msr3d_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------

@@ -365,6 +365,123 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const FA a) {
   own_store<D>(dk, a.scale, a.dk + rowoff, g);
 }
 
+// =====================================================================================================
+// prefix-shared forward (closed-set answer ranking, msr3d_amd/llm/generate.py::CachedDecoder.score): C candidates of
+// S suffix tokens each attend to ONE cached prefix of their prompt and causally to their own suffix.  The forward
+// kernel's machinery with two differences: the key blocks are the prefix's ceil(len / 64) blocks of the cache (the last
+// one partial: rows >= len are staged as zeros, so neither a stale nor a NaN bit pattern of an unused slot reaches a
+// product) followed by the workgroup's OWN 64 suffix rows, where "visible" is "same candidate and not later"; and the
+// last query tile of a (prompt, head) may hold fewer than 64 rows (staged as zeros, not stored).
+// Workgroup numbering: the tiles of one (prompt, head) are 8 apart, so that under round-robin dispatch over the eight
+// XCDs they share one L2 and the prefix is fetched from memory once per (prompt, head); speed only.
+// =====================================================================================================
+struct PA {
+  int BH, H, C, S, Tmax, ld, ldo, sshift, nq, plain;
+  const u16 *q, *k, *v, *kc, *vc;
+  u16 *o;
+  const int *len;
+  const unsigned char *pkeep, *skeep;
+  float c;                                  // scale * log2(e)
+};
+
+// tile_fetch with the rows >= nrows as zeros (never addressed)
+template <int D>
+__device__ __forceinline__ void tile_fetch_rows(u32x4 (&t)[D / 32], const u16 *base, int ld, int tid, int nrows) {
+  constexpr int CPR = D / 8;
+#pragma unroll
+  for (int u = 0; u < D / 32; ++u) {
+    const int c = tid + 256 * u, row = c / CPR, col = (c % CPR) * 8;
+    t[u] = row < nrows ? *reinterpret_cast<const u32x4 *>(base + (unsigned)(row * ld + col)) : u32x4{0u, 0u, 0u, 0u};
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256, 4) void attn_prefix_kernel(const PA a) {
+  constexpr int P = D + 8, NDT = D / 16;
+  __shared__ __attribute__((aligned(16))) u16 ks_[BLK * P];
+  __shared__ __attribute__((aligned(16))) u16 vs_[BLK * P];
+  __shared__ __attribute__((aligned(16))) unsigned char kp_[BLK];   // the staged block's key flags
+  const int slot = a.plain ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
+  const int bh = a.plain ? slot / a.nq : (slot / a.nq) * 8 + (int)(blockIdx.x & 7), qt = slot % a.nq;
+  if (bh >= a.BH) return;                                      // (B H not a multiple of 8: whole workgroups)
+  const int b = bh / a.H, h = bh % a.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+  const int rows = a.C * a.S;                                  // suffix rows of one prompt
+  const int r0 = qt * BLK, qloc = 16 * wave + j;              // this lane's query: row r0 + qloc of the prompt's suffix rows
+  const int nown = min(BLK, rows - r0);                        // real rows of this tile (a multiple of S)
+  const bool qok = qloc < nown;
+  const size_t sbase = (size_t)b * rows + r0;
+  const size_t HD = (size_t)a.H * D;
+  bf16x8 qf[D / 32];
+  if (qok) own_fetch<D>(qf, a.q + (sbase + qloc) * a.ld + (size_t)h * D, g);
+  else {
+#pragma unroll
+    for (int ks = 0; ks < D / 32; ++ks) qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  }
+  int L = a.len[b];
+  L = L < 0 ? 0 : (L > a.Tmax ? a.Tmax : L);                   // clamped before it forms an address
+  const int npre = (L + BLK - 1) / BLK;
+  const u16 *kcb = a.kc + (size_t)b * a.Tmax * HD + (size_t)h * D, *vcb = a.vc + (size_t)b * a.Tmax * HD + (size_t)h * D;
+  const unsigned char *pk = a.pkeep + (size_t)b * a.Tmax;
+  const u16 *ksb = a.k + sbase * a.ld + (size_t)h * D, *vsb = a.v + sbase * a.ld + (size_t)h * D;
+  f32x4 oacc[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+  for (int kb = 0; kb <= npre; ++kb) {
+    const bool own = kb == npre;                               // the last block: this tile's own suffix keys
+    const int k0 = kb * BLK;
+    {
+      Tile<D> kt, vt;
+      const int n = own ? nown : min(BLK, L - k0);             // real rows of the block; the others are staged as zeros
+      const int tld = own ? a.ld : (int)HD;
+      const unsigned char *fp = own ? (a.skeep ? a.skeep + sbase : nullptr) : pk + k0;
+      tile_fetch_rows<D>(kt, own ? ksb : kcb + (size_t)k0 * HD, tld, tid, n);
+      tile_fetch_rows<D>(vt, own ? vsb : vcb + (size_t)k0 * HD, tld, tid, n);
+      const unsigned char flag = tid < n ? (fp ? fp[tid] : (unsigned char)1) : (unsigned char)0;
+      __syncthreads();                                         // the previous block's readers are done
+      tile_store<D>(kt, ks_, tid);
+      tile_store<D>(vt, vs_, tid);
+      if (tid < BLK) kp_[tid] = flag;
+    }
+    __syncthreads();
+    f32x4 s[4];
+    mma_rows<D>(s, ks_, qf, lane);                             // s[t][r] = <key 16 t + 4 g + r of the block, q[qrow]>
+    float x[4][4], mloc = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const unsigned kp = *reinterpret_cast<const unsigned *>(kp_ + 16 * t + 4 * g);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = 16 * t + 4 * g + r;
+        const bool vis = ((kp >> (8 * r)) & 0xffu) && (!own || ((key >> a.sshift) == (qloc >> a.sshift) && key <= qloc));
+        x[t][r] = vis ? s[t][r] * a.c : -INFINITY;
+        mloc = fmaxf(mloc, x[t][r]);
+      }
+    }
+    mloc = row_max(mloc);
+    const float m_new = fmaxf(m_run, mloc);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = ex2(m_run - m_use);
+    float lsum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { x[t][r] = ex2(x[t][r] - m_use); lsum += x[t][r]; }
+    l_run = l_run * alpha + row_sum(lsum);
+    m_run = m_new;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) { oacc[dt][0] *= alpha; oacc[dt][1] *= alpha; oacc[dt][2] *= alpha; oacc[dt][3] *= alpha; }
+    const bf16x8 pf[2] = {pack_frag(x[0], x[1]), pack_frag(x[2], x[3])};
+    mma_transposed<D>(oacc, vs_, pf, lane);                    // o[qrow][d] += sum_key p[key] v[key][d]
+  }
+  const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+  if (qok) own_store<D>(oacc, inv, a.o + (sbase + qloc) * a.ldo + (size_t)h * D, g);
+}
+
+// workgroup numbering of the prefix-shared forward: 0 = a (prompt, head)'s tiles 8 apart (default), 1 = adjacent
+int g_prefix_order = 0;
+
 inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 bool shape_ok(int B, int T, int H, int D, int ld) {
@@ -391,6 +508,38 @@ int msr3d_attn_fwd(int B, int T, int H, int D, const void *q, const void *k, con
   if (D == 128) attn_fwd_kernel<128><<<grid, 256, 0, (hipStream_t)stream>>>(a);
   else attn_fwd_kernel<64><<<grid, 256, 0, (hipStream_t)stream>>>(a);
   return (int)hipGetLastError();
+}
+
+int msr3d_attn_prefix_fwd(int B, int C, int S, int Tmax, int H, int D, const void *q, const void *k, const void *v, int ld,
+                          const void *k_cache, const void *v_cache, const int *len, const unsigned char *prefix_keep,
+                          const unsigned char *suffix_keep, float scale, void *out, int ldo, msr3d_stream_t stream) {
+  if (B < 0 || C < 0 || Tmax < 0 || H <= 0 || (D != 64 && D != 128) || (S != 16 && S != 32 && S != 64) ||
+      (long long)H * D > (1 << 24) || ld < H * D || ld > (1 << 24) || (ld % 8) != 0 || ldo < H * D || (ldo % 8) != 0)
+    return MSR3D_EINVAL;
+  if (B == 0 || C == 0) return 0;
+  const long long rows = (long long)C * S, nq = (rows + BLK - 1) / BLK, groups = ((long long)B * H + 7) / 8;
+  if ((long long)B * rows > 0x7fffffffLL || 8 * groups * nq > 0x7fffffffLL) return MSR3D_EINVAL;
+  if (!q || !k || !v || !out || !len || !al16(q) || !al16(k) || !al16(v) || (reinterpret_cast<uintptr_t>(out) & 7u))
+    return MSR3D_EINVAL;
+  if (Tmax > 0 && (!k_cache || !v_cache || !prefix_keep || !al16(k_cache) || !al16(v_cache))) return MSR3D_EINVAL;
+  PA a{};
+  a.BH = B * H; a.H = H; a.C = C; a.S = S; a.Tmax = Tmax; a.ld = ld; a.ldo = ldo;
+  a.sshift = S == 16 ? 4 : (S == 32 ? 5 : 6);
+  a.nq = (int)nq;
+  a.q = (const u16 *)q; a.k = (const u16 *)k; a.v = (const u16 *)v; a.kc = (const u16 *)k_cache; a.vc = (const u16 *)v_cache;
+  a.o = (u16 *)out; a.len = len; a.pkeep = prefix_keep; a.skeep = suffix_keep;
+  a.c = scale * 1.4426950408889634f;
+  a.plain = g_prefix_order;
+  const unsigned grid = (unsigned)(a.plain ? (long long)B * H * nq : 8 * groups * nq);
+  if (D == 128) attn_prefix_kernel<128><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  else attn_prefix_kernel<64><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  return (int)hipGetLastError();
+}
+
+int msr3d_attn_prefix_order(int order) {
+  if (order == 0 || order == 1) g_prefix_order = order;
+  else if (order != -1) return MSR3D_EINVAL;
+  return g_prefix_order;
 }
 
 int msr3d_attn_bwd(int B, int T, int H, int D, const void *q, const void *k, const void *v, const void *out,

@@ -2,7 +2,7 @@
 decode kernels of csrc/llm_decode.hip (what transformers' `LlamaForCausalLM.generate(inputs_embeds=..., attention_mask=...,
 num_beams=..., repetition_penalty=..., length_penalty=...)` computes; the reference's MSR3D.generate calls exactly that).
 
-Three pieces:
+Four pieces:
 
 * `KVCache`        the buffers of one call: K / V (layers, 2, rows, t_max, heads, head_dim) bf16, token-major like the
                    projections' own output, twice when beams are reordered (ping-pong), and per row `len` (cache slots in
@@ -17,6 +17,11 @@ Three pieces:
 * `search`         greedy / beam search with transformers' semantics, written against the engine interface alone
                    (`reserve`, `prefill`, `expand`, `step`, and optionally `select`), so it runs on the CPU with any
                    engine: that is how its logic is checked exactly against transformers.
+* `rank_answers`   closed-set answer ranking (the reference's MSR3D.predict_answers): the prompt is prefilled ONCE per
+                   row (`prefill(positions="arange")`: the positions of the full forward), the candidate answers run
+                   through `CachedDecoder.score` as B x C short suffixes that attend to that one cached prefix
+                   (msr3d_attn_prefix_fwd, csrc/llm_attn.hip) instead of C copies of prompt + answer through the full
+                   forward.  Written against the engine interface alone (`prefill`, `score`), like `search`.
 
 `max_length` counts GENERATED tokens (the prompt travels as embeddings and has no ids).  GPU only for the engine."""
 import ctypes
@@ -159,6 +164,62 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
     return fin_seq[:, 0, :int(fin_len[:, 0].max())]
 
 
+# ---------------------------------------------------------------------------------------------------- answer ranking
+@torch.no_grad()
+def rank_answers(engine, embed_fn, inputs_embeds, attention_mask, answer_ids, answer_mask, num_ans_candidates=128,
+                 bos_id=None):
+    """Closed-set answer ranking, the reference's MSR3D.predict_answers step for step, on ONE cached copy of each prompt.
+    engine: `prefill(inputs_embeds (B, T, H), attention_mask (B, T), positions="arange") -> (B, V)` logits of the last
+    position and `score(token_embeds (B, C, S, H), token_keep (B, C, S)) -> (B, C, S, V)` logits after each suffix token.
+    answer_ids (A, S) int64 right-padded, answer_mask (A, S); every answer starts with the same token (bos), which is the
+    LAST slot of the cached prompt: with `bos_id` given it is appended here (its embedding and a mask column of ones),
+    without it the prompt must already end with it.
+    1. p = softmax(prefill logits); first_prob = p[:, answer_ids[:, 1]]; the C = min(num_ans_candidates, A) most
+       probable answers of every prompt -> topk_ids (B, C);
+    2. loss[b, c] = the mean over the real tokens a_1 .. of candidate c of the cross-entropy of predicting each from its
+       predecessor (a_1 from the prefill logits, the others from `score`), fp32 log-sum-exp;
+    3. answers_id[b] = topk_ids[b, argmin_c loss[b, c]].
+    -> dict(answers_id (B,), topk_ids (B, C) int64, loss (B, C) fp32, first_prob (B, A) fp32)."""
+    from .losses import seq_mean_cross_entropy
+    x, mask = inputs_embeds, attention_mask
+    dev = x.device
+    ids = answer_ids.to(dev).long()
+    am = answer_mask.to(dev).bool()
+    if ids.dim() != 2 or ids.shape != am.shape or ids.shape[1] < 2 or ids.shape[0] < 1:
+        raise ValueError("rank_answers: answer_ids / answer_mask (A, S) with S >= 2 (bos + at least one token)")
+    first = int(ids[0, 0])
+    if not bool((ids[:, 0] == first).all()) or (bos_id is not None and first != int(bos_id)):
+        raise ValueError("rank_answers: every answer must start with the same token (bos)")
+    if not bool(am[:, 1].all()):
+        raise ValueError("rank_answers: an answer without a real token after bos (its mean loss would be 0 / 0)")
+    if bos_id is not None:
+        bos = embed_fn(torch.full((x.shape[0],), first, dtype=torch.int64, device=dev)).to(x.dtype)
+        x = torch.cat([x, bos[:, None]], 1)
+        mask = torch.cat([mask, torch.ones_like(mask[:, :1])], 1)
+    B, A = x.shape[0], ids.shape[0]
+    C = min(int(num_ans_candidates), A)
+    if C < 1:
+        raise ValueError("rank_answers: num_ans_candidates >= 1")
+    if hasattr(engine, "reserve"):
+        engine.reserve(1, 0)                                                      # one cache row per prompt, no new slots
+    logits0 = engine.prefill(x, mask, positions="arange")                         # (B, V)
+    first_prob = torch.softmax(logits0.float(), dim=1).index_select(1, ids[:, 1])  # (B, A)
+    topk_ids = first_prob.topk(C, dim=1)[1]                                       # (B, C)
+    suffix, keep = ids[:, 1:][topk_ids], am[:, 1:][topk_ids]                      # (B, C, S - 1)
+    S = suffix.shape[2]
+    emb = embed_fn(suffix.reshape(-1)).view(B, C, S, -1)
+    lg = engine.score(emb, keep)                                                  # (B, C, S, V)
+    V = lg.shape[-1]
+    # per candidate the sequence [prefill logits, suffix logits] against the targets [-, a_1, a_2, ..]: logits[t] is read
+    # against targets[t + 1], so the last suffix position's logits and targets[0] take no part
+    seq = torch.cat([logits0.to(lg.dtype)[:, None, None].expand(B, C, 1, V), lg], 2).reshape(B * C, S + 1, V)
+    tg = torch.where(keep, suffix, torch.full_like(suffix, -100))
+    tg = torch.cat([torch.full_like(tg[:, :, :1], -100), tg], 2).reshape(B * C, S + 1)
+    loss = seq_mean_cross_entropy(seq, tg).float().view(B, C)
+    best = loss.argmin(dim=1)
+    return dict(answers_id=topk_ids.gather(1, best[:, None])[:, 0], topk_ids=topk_ids, loss=loss, first_prob=first_prob)
+
+
 # ------------------------------------------------------------------------------------------------------------ cache
 class KVCache:
     """kv[side] (layers, 2, rows, t_max, heads, head_dim) bf16, side = `cur` is the live one (two sides only with
@@ -225,7 +286,13 @@ class CachedDecoder:
 
     # -- prefill ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def prefill(self, inputs_embeds, attention_mask):
+    def prefill(self, inputs_embeds, attention_mask, positions="mask"):
+        """-> (B, V) logits of the last position; every layer's K / V of the prompt go into the cache.
+        positions = "mask": slot t is rotated by cumsum(mask)[t] - 1 and the next position is the number of unmasked
+        tokens (what transformers' `generate` feeds Llama); "arange": slot t is rotated by t and the next position is T
+        (what transformers' LlamaModel.forward does when it is called with a mask and no position_ids, i.e. what
+        LoRALlamaStack.logits computes: the full forward `score` continues).  The two differ when the prompt has masked
+        slots inside it."""
         from .decoder import _AttentionFn, _RMSNormFn, _SwiGLUFn, rope_tables
         from .lora import refresh_shadows
         st = self.stack
@@ -244,7 +311,12 @@ class CachedDecoder:
             mask = torch.cat([mask, torch.zeros((B, Tp - T), dtype=torch.bool, device=dev)], 1)
         x = x.contiguous()
         keep = mask.to(torch.uint8).contiguous()
-        pos = (mask.long().cumsum(-1) - 1).clamp_min(0).to(torch.int32).contiguous()
+        if positions == "mask":
+            pos = (mask.long().cumsum(-1) - 1).clamp_min(0).to(torch.int32).contiguous()
+        elif positions == "arange":
+            pos = torch.arange(Tp, dtype=torch.int32, device=dev)[None].expand(B, Tp).contiguous()
+        else:
+            raise ValueError("CachedDecoder.prefill: positions is 'mask' or 'arange'")
         t_max = T + new_tokens
         cache = self.cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1)
         rows = max(t_max, Tp)
@@ -271,7 +343,7 @@ class CachedDecoder:
             x, delta = x1, y
         _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
         cache.len[first] = T
-        cache.pos[first] = mask.sum(-1).to(torch.int32)
+        cache.pos[first] = mask.sum(-1).to(torch.int32) if positions == "mask" else T
         cache.keep[first, :T] = keep[:, :T]
         return st.lm_head(h)[:, 0]
 
@@ -287,6 +359,75 @@ class CachedDecoder:
         for t in (c.len, c.pos, c.keep):
             g = t.view(B, beams, *t.shape[1:])
             g[:, 1:] = g[:, :1]
+
+    # -- many suffixes on one cached prefix ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def score(self, token_embeds, token_keep, max_rows=8192):
+        """token_embeds (B, C, S, hidden), token_keep (B, C, S) (0 = padded slot) -> logits (B, C, S, V) bf16: row
+        (b, c, j) is the next-token distribution after prompt b (the cache a `prefill` with one row per prompt left)
+        followed by tokens 0 .. j of candidate c, at rotary positions pos[b] + j.  Every layer runs over the B C S suffix
+        rows alone with the layer forward's kernels; attention is msr3d_attn_prefix_fwd against the cached prefix.  The
+        cache is read, never written: `score` may be called again after one `prefill`.  Candidates are walked in chunks of
+        at most `max_rows` suffix rows (every row's arithmetic is its own: the result does not depend on the chunking)."""
+        from .decoder import _RMSNormFn, _SwiGLUFn, rope_tables
+        from .lora import refresh_shadows
+        st, c = self.stack, self.cache
+        if c is None:
+            raise RuntimeError("CachedDecoder.score before prefill")
+        if self._plan[0] != 1:
+            raise RuntimeError("CachedDecoder.score: the cache holds beams (prefill with one row per prompt)")
+        if not token_embeds.is_cuda:
+            raise RuntimeError("CachedDecoder runs on the GPU only (no CPU fallback)")
+        B, C, S, Hd = token_embeds.shape
+        if B != c.rows or Hd != self.hidden or tuple(token_keep.shape) != (B, C, S):
+            raise ValueError("CachedDecoder.score: token_embeds (rows, C, S, hidden) and token_keep (rows, C, S)")
+        if not 1 <= S <= 64:
+            raise ValueError("CachedDecoder.score: 1 .. 64 suffix tokens")
+        H, D, HD, dev = self.H, self.D, self.H * self.D, token_embeds.device
+        Sp = 16 if S <= 16 else (32 if S <= 32 else 64)         # the kernel's suffix sizes; the extra slots are masked
+        x_all = token_embeds.to(torch.bfloat16)
+        keep_all = token_keep.to(dev).bool()
+        if Sp != S:
+            x_all = torch.cat([x_all, torch.zeros((B, C, Sp - S, Hd), dtype=x_all.dtype, device=dev)], 2)
+            keep_all = torch.cat([keep_all, torch.zeros((B, C, Sp - S), dtype=torch.bool, device=dev)], 2)
+        cos, sin, rows = self._tables
+        if rows < c.t_max + Sp:                                # (positions are at most len + Sp - 1 <= t_max + Sp - 1)
+            rows = c.t_max + Sp
+            cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
+            self._tables = (cos, sin, rows)
+        refresh_shadows(self.mods, False)
+        scale = 1.0 / math.sqrt(D)
+        V = st.lm_head.out_features
+        out = torch.empty((B, C, S, V), dtype=torch.bfloat16, device=dev)
+        step = max(1, int(max_rows) // (B * Sp))
+        last = len(st.layers) - 1
+        for c0 in range(0, C, step):
+            Cc = min(step, C - c0)
+            N = B * Cc
+            x = x_all[:, c0:c0 + Cc].reshape(N, Sp, Hd).contiguous()
+            skeep = keep_all[:, c0:c0 + Cc].reshape(N, Sp).to(torch.uint8).contiguous()
+            pos = (c.pos[:, None, None] + torch.arange(Sp, dtype=torch.int32, device=dev)).expand(B, Cc, Sp)
+            pos = pos.reshape(N, Sp).contiguous()
+            delta = None
+            for i, layer in enumerate(st.layers):
+                a, m = layer.self_attn, layer.mlp
+                x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
+                q, k, v = a["q_proj"].forward2d(h), a["k_proj"].forward2d(h), a["v_proj"].forward2d(h)
+                ctx = torch.empty((N * Sp, HD), dtype=torch.bfloat16, device=dev)
+                with torch.cuda.device(dev):
+                    s = _lib.current_stream_ptr(dev)
+                    _call("msr3d_rope_positions", N, Sp, H, D, _p(q), _p(k), _p(pos), _p(cos), _p(sin), rows, s)
+                    _call("msr3d_attn_prefix_fwd", B, Cc, Sp, c.t_max, H, D, _p(q), _p(k), _p(v), HD, _p(c.k(i)), _p(c.v(i)),
+                          _p(c.len), _p(c.keep), _p(skeep), ctypes.c_float(scale), _p(ctx), HD, s)
+                o = a["o_proj"](ctx.view(N, Sp, HD))
+                if i == last and Sp != S:                      # the padded slots' logits are not wanted
+                    x0, o = x0[:, :S].contiguous(), o[:, :S].contiguous()
+                x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
+                y = m["down_proj"](_SwiGLUFn.apply(m["gate_proj"](h2), m["up_proj"](h2)))
+                x, delta = x1, y
+            _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
+            out[:, c0:c0 + Cc] = st.lm_head(h).view(B, Cc, S, V)
+        return out
 
     # -- one token ------------------------------------------------------------------------------------------------
     def _products(self, h, mods, swiglu=False):
@@ -397,3 +538,10 @@ def generate(stack, inputs_embeds, attention_mask, embed_tokens, **search_kwargs
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings)."""
     embed_fn = embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
     return search(CachedDecoder(stack), embed_fn, inputs_embeds, attention_mask, **search_kwargs)
+
+
+@torch.no_grad()
+def predict_answers(stack, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs):
+    """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder; rank_kwargs: num_ans_candidates, bos_id."""
+    embed_fn = embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
+    return rank_answers(CachedDecoder(stack), embed_fn, inputs_embeds, attention_mask, answer_ids, answer_mask, **rank_kwargs)

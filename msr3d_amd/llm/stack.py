@@ -160,6 +160,13 @@ class LoRALlamaStack(nn.Module):
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs)
 
+    def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs):
+        """Closed-set answer ranking on one cached copy of every prompt (msr3d_amd/llm/generate.py::rank_answers) ->
+        dict(answers_id (B,), topk_ids (B, C), loss (B, C) fp32, first_prob (B, A)).  answer_ids / answer_mask (A, S):
+        the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id."""
+        from .generate import predict_answers
+        return predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs)
+
     def forward(self, inputs_embeds, attention_mask=None, targets=None, supervised_from=None):
         """-> logits (B, T, V) bf16, or with `targets` (B, T) int64 (negative = not supervised) the per-sequence mean
         cross-entropy (B,) of msr3d.py:426-441.

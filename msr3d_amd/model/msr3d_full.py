@@ -10,9 +10,11 @@
 
 What is NOT here (out of SURVEY §8's scope): tokenizer and prompt assembly (the step takes
 token ids), the 2D image branch (`image_encoder`, `llm_proj_img`: one placeholder token per sequence), CLIP fusion, and of the reference's `generate`
-everything but greedy / beam search: nucleus sampling, `num_captions > 1`, `pred_action`, `predict_answers`.
+everything but greedy / beam search: nucleus sampling, `num_captions > 1`, `pred_action`.
 `MSR3DFullStep.generate` is the reference's evaluation path (msr3d.py:445-524): prompt embeddings + scene tokens + one bos
-embedding -> KV-cached beam search (msr3d_amd/llm/generate.py) -> `output_tokens`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
+embedding -> KV-cached beam search (msr3d_amd/llm/generate.py) -> `output_tokens`.  `MSR3DFullStep.predict_answers` is
+its closed-vocabulary path (msr3d.py:526-655): the same prompt, prefilled once, and the candidate answers scored as
+short suffixes on that one cache (`rank_answers`) -> `answers_id`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
 under `llm_model.*` (msr3d_amd/llm/checkpoint.py maps Hugging Face / peft keys onto it).
 
 GPU only beyond the prompter: the language-model kernels have no CPU fallback."""
@@ -120,4 +122,35 @@ class MSR3DFullStep(MSR3DHotPath):
         out = torch.where(out == 0, torch.full_like(out, 2), out)
         pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
         d["output_tokens"] = torch.cat([out, pad], 1)
+        return d
+
+    @torch.no_grad()
+    def predict_answers(self, data_dict, answer_ids, answer_mask, num_ans_candidates=128, bos_id=1, answer_list=None):
+        """The reference's MSR3D.predict_answers: hot path -> prompt embeddings with the scene tokens written in and the
+        object mask at their positions -> one bos embedding and a mask column of ones appended -> the `num_ans_candidates`
+        answers whose first token is most probable -> the one with the smallest mean token loss ->
+        data_dict['answers_id'] (B,) int64 on the device (indices into the answer list), plus 'answers_topk_ids' (B, C),
+        'answers_loss' (B, C) fp32 and, with `answer_list` (the strings), 'answers'.  answer_ids / answer_mask (A, S) int64:
+        the tokenised answer list, bos first, right-padded (tokenising stays outside, like all tokenising here)."""
+        if not data_dict["input_ids"].is_cuda:
+            raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
+        if answer_list is not None and len(answer_list) != answer_ids.shape[0]:
+            raise ValueError("answer_list and answer_ids disagree on the number of answers")
+        # (deterministic hot path: see generate -- a flipped bf16 scene token could flip a close ranking)
+        from .. import hipops
+        was = hipops.set_deterministic(True)
+        try:
+            d = MSR3DHotPath.forward(self, data_dict)
+        finally:
+            hipops.set_deterministic(was)
+        ids = data_dict["input_ids"].contiguous()
+        am = data_dict["attention_mask"].to(torch.int64).contiguous().clone()
+        emb = F.embedding(ids, self.embed_tokens).contiguous()
+        scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
+        out = self.llm_model.predict_answers(emb, am, self.embed_tokens, answer_ids, answer_mask,
+                                             num_ans_candidates=num_ans_candidates, bos_id=bos_id)
+        d["answers_id"] = out["answers_id"]
+        d["answers_topk_ids"], d["answers_loss"] = out["topk_ids"], out["loss"]
+        if answer_list is not None:
+            d["answers"] = [answer_list[i] for i in out["answers_id"].tolist()]
         return d
