@@ -88,9 +88,22 @@ __global__ __launch_bounds__(kDotThreads) void dot_kernel(long long n4, const fl
     // The partial must be visible to the LAST block, possibly on another XCD, before the ticket is.  An agent-scope
     // release fence does that by writing the XCD's whole L2 back (buffer_wbl2): 23-27 k cycles a block
     // (profiles/r06_last_arriver_probe.txt), most of this kernel's 12 us.  Instead the partial itself travels by a
-    // RETURNING read-modify-write -- device-scope atomics execute at the memory side of the fabric on this part
-    // (TCC_EA0_ATOMIC == TCC_ATOMIC), and its return value says it has -- the ticket is taken only then, and the last
-    // block reads the partials back the same way (an atomic OR of 0): no cache is written back or invalidated.
+    // RETURNING read-modify-write (global_atomic_swap sc0) -- device-scope atomics execute at the memory side of the
+    // fabric on this part (TCC_EA0_ATOMIC == TCC_ATOMIC) and leave no line behind in the XCD's L2; its return value,
+    // waited for below, says it has executed -- and the ticket (global_atomic_add sc0) is taken only then.  No cache is
+    // written back or invalidated.
+    // The READ side is not a read-modify-write, whatever the source below looks like: for gfx950 the compiler turns
+    // the relaxed agent-scope fetch_or(.., 0) into a plain agent-scope load (global_load_dword sc1), which bypasses
+    // this CU's L1 and is served by this XCD's L2.  What the kernel relies on, then, is (1) that no line of `partial`
+    // is resident in that L2 when the last block loads it: nothing in this kernel reads or plainly stores `partial`
+    // before the ticket says all blocks have swapped, atomics drop the line, and a line a previous launch's last
+    // block loaded is invalidated at the kernel boundary; (2) that the loads issue after the ticket's value has
+    // returned: thread 0 waits for it before the barrier every loading thread passes; (3) that every swap returned
+    // before its block's add was issued (the asm wait).  This is a hand-off gfx950 has been measured to honour, not
+    // one the memory model promises: in the model's terms the swap/add pair lacks a release and the load an acquire.
+    // tests/test_optim_gpu.py checks it by value only: exact integer sums over 200 back-to-back launches whose grids
+    // change on one scratch.  Should that ever fail, the repair is an agent acquire fence between the ticket and
+    // the loads (and a release in front of the add), at the price quoted above.
     const int prev = __hip_atomic_exchange(reinterpret_cast<int *>(partial) + blockIdx.x, __float_as_int(blk), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");

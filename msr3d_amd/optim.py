@@ -82,16 +82,43 @@ class FlatAdamW:
         for q in self.dp.order:
             inc(q)
 
-    def set_unused(self, params):
+    def set_unused(self, params, names=None):
         """Parameters that receive no gradient in this configuration (`anchor_feat`, `loc_layers` with
         situation_type 'as_transform_for_objects', a classification head nobody reads): torch.optim.AdamW
         skips a parameter whose .grad is None -- no moment update, NO weight decay -- and the reference
         trains exactly so (DDP with find_unused_parameters=True, trainer/leo_trainer.py:50-52).  Here
-        every parameter has a (zero) gradient view, so the set is stated: these are left untouched."""
+        every parameter has a (zero) gradient view, so the set is stated: these are left untouched.
+
+        The kernel's mask has one byte per float4.  A parameter, or a whole pack group, starts on a float4
+        boundary, but the members of a pack group sit back to back (dp.py), so the first or last float4 of an
+        unused member can also hold elements of a neighbour.  If that neighbour is not unused as well, masking
+        the float4 would freeze up to 3 of its elements: ValueError, naming the unused parameter (by
+        `names[i]`, the parameter names in `dp.order`, or by its position there).  A gap, the tail padding
+        or another unused parameter in that float4 is fine."""
+        params = list(params)
+        if names is not None and len(names) != len(self.dp.order):
+            raise ValueError("names must have one entry per parameter of dp.order")
+        unused = {id(p) for p in params}
+        index = {id(q): i for i, q in enumerate(self.dp.order)}
+        used = [(self.dp.offset[id(q)], q.numel(), q) for q in self.dp.order if id(q) not in unused]
+
+        def label(q):
+            i = index[id(q)]
+            return names[i] if names is not None else f"dp.order[{i}] (shape {tuple(q.shape)})"
         n4 = self.flat_p.numel() // 4
         act = torch.ones(n4, dtype=torch.uint8, device=self.flat_p.device)
         for p in params:
-            off, k = self.dp.offset[id(p)], p.numel()         # (offsets are multiples of 4 elements)
+            off, k = self.dp.offset[id(p)], p.numel()
+            if k == 0:
+                continue
+            for lo in sorted({off // 4 * 4, (off + k - 1) // 4 * 4}):      # the float4 of p's first / last element
+                for o, n, q in used:
+                    if o < lo + 4 and o + n > lo:
+                        raise ValueError(
+                            f"set_unused: {label(p)} (elements {off}..{off + k - 1} of the flat buffer) shares the "
+                            f"float4 at {lo} with {label(q)}, which receives gradients; the per-float4 mask cannot "
+                            "separate them -- pad the pack group's members to multiples of 4 elements, or leave "
+                            "the parameter out of the group")
             act[off // 4:(off + k + 3) // 4] = 0
         self.active = act if int((act == 0).sum()) else None
         self.unused = [id(p) for p in params]
