@@ -41,6 +41,7 @@ def test_add_layernorm_matches_torch(M, D, with_r):
 
 def test_dropout_mask_statistics_and_backward_consistency():
     from msr3d_amd import hipops
+    from tests import dropout_ref
     torch.manual_seed(0)
     M, D, p = 2048, 256, 0.1
     ln = torch.nn.LayerNorm(D).cuda()
@@ -48,10 +49,13 @@ def test_dropout_mask_statistics_and_backward_consistency():
     # a = large constant + tiny noise, so y ~ pattern of kept/dropped elements
     a = torch.ones(M, D, device="cuda", requires_grad=True)
     y1 = hipops.dropout_add_layernorm(a, None, ln, p, training=True)
+    salt1 = hipops._salt_counter[0]                                      # the salt that call drew
     y2 = hipops.dropout_add_layernorm(a, None, ln, p, training=True)     # new salt -> new mask
     kept1 = (y1 > 0).float()          # rows are {0, 1/(1-p)} patterns: kept elements land above the mean
     frac = 1.0 - kept1.mean().item()
     assert abs(frac - p) < 0.01, frac
+    host = dropout_ref.keep_mask(dropout_ref.u64(hipops.seed_word(a.device).item()), salt1, M, D, D, p)
+    assert torch.equal(kept1.bool(), torch.from_numpy(host).cuda())      # the kept pattern is the host statement's
     assert (kept1 != (y2 > 0).float()).float().mean().item() > 0.05
     # backward uses the SAME mask as forward: d(sum y * w)/da is zero exactly where dropped
     w = torch.randn(M, D, device="cuda")
