@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 31
+#define MSR3D_ABI_VERSION 32
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -783,13 +783,6 @@ typedef struct msr3d_scene_block {
 } msr3d_scene_block_t;
 
 int msr3d_scene_block(const msr3d_scene_block_t *p, msr3d_stream_t stream);
-/* The attention forward block's launch form: 1 (the library's default; MSR3D_ATTN_FWD_SPLIT=0 in the environment selects 0
- * at first use) = two workgroups per (scene, head), each 32 query rows, keys split over eight waves: the faster form when
- * the step has the chip to itself; 0 = one workgroup per (scene, head) -- 128 workgroups at the bench shape: slower alone
- * (19.3 against 16 us), FASTER in the pipelined schedule, where the next batch's frozen encoder runs beside the trainable
- * part and takes the CUs this form leaves (round 6: 0.851 against 0.863 ms a step).  Same values either way.
- * form = 0 / 1 selects, -1 only queries; returns the form in force, MSR3D_EINVAL for another value. */
-int msr3d_attn_fwd_form(int form);
 
 /* One wave per token row: a0 = sum_s part[s] (+ extra) (+ a0_bias) in slab order (nslab == 0: a0 itself),
  * optionally stored whole (sum_out); then the MSR3D_PRO_* chain with the operands / outputs of
@@ -853,21 +846,16 @@ int msr3d_wgrad_split(int n, const msr3d_wgrad_problem_t *problems, const int *t
 int msr3d_wgrad_split_colsum(int n, const msr3d_wgrad_problem_t *problems, const int *tile_prefix, int total_tiles,
                              int n_jobs, const msr3d_colsum_job_t *jobs, msr3d_stream_t stream);
 
-/* The same launch with every tile's token reduction cut in TWO units (2 x total_tiles workgroups) so that a step's
- * ~1.4 tiles per CU spread evenly over the chip.  The unit that STARTS first parks its 128 x 128 partial in the
- * tile's workspace slot, the one that starts second adds first half + second half -- in that order, whichever of
- * them it is -- onto dW: still no float atomics, still bit-reproducible, identical sums for both launch forms only
- * up to fp32 association.  workspace: total_tiles x MSR3D_WGRAD_HALF_SLOT_FLOATS floats; sync: 2 x total_tiles
- * ints, ZERO before the first launch (every launch leaves them zero).  total_tiles % 8 == 0. */
-#define MSR3D_WGRAD_HALF_SLOT_FLOATS (128 * 128 + 128)
-int msr3d_wgrad_split_halves(int n, const msr3d_wgrad_problem_t *problems, const int *tile_prefix, int total_tiles,
-                             float *workspace, long long workspace_floats, int *sync, msr3d_stream_t stream);
 /* MIXED form (round 5): only the tiles of the launch's PARTIAL round are cut.  Workgroups [0, whole_tiles) take whole
- * tiles, the other H = total_tiles - whole_tiles tiles run as two half-reductions each (the protocol above), n_jobs
- * column-sum workgroups follow (msr3d_wgrad_split_colsum).  The caller picks whole_tiles so that the halves fill what the
- * whole tiles leave of the chip's second round (msr3d_amd/scene_blocks.py: real tiles beyond one per CU, when they are at
- * most half a round).  whole_tiles % 8 == 0 and H % 8 == 0; workspace: H x MSR3D_WGRAD_HALF_SLOT_FLOATS floats; sync:
- * 2 H ints, zero before the first launch.  H == 0 is msr3d_wgrad_split_colsum. */
+ * tiles, the other H = total_tiles - whole_tiles tiles run as two half-reductions each, n_jobs column-sum workgroups
+ * follow (msr3d_wgrad_split_colsum).  Of a cut tile's two units the one that STARTS first parks its 128 x 128 partial in
+ * the tile's workspace slot, the one that starts second adds first half + second half -- in that order, whichever of
+ * them it is -- onto dW: still no float atomics, still bit-reproducible, identical sums to msr3d_wgrad_split only up to
+ * fp32 association.  The caller picks whole_tiles so that the halves fill what the whole tiles leave of the chip's
+ * second round (msr3d_amd/scene_blocks.py: real tiles beyond one per CU, when they are at most half a round).
+ * whole_tiles % 8 == 0 and H % 8 == 0; workspace: H x MSR3D_WGRAD_HALF_SLOT_FLOATS floats; sync: 2 H ints, ZERO before
+ * the first launch (every launch leaves them zero).  H == 0 is msr3d_wgrad_split_colsum. */
+#define MSR3D_WGRAD_HALF_SLOT_FLOATS (128 * 128 + 128)
 int msr3d_wgrad_split_mixed(int n, const msr3d_wgrad_problem_t *problems, const int *tile_prefix, int total_tiles,
                             int whole_tiles, int n_jobs, const msr3d_colsum_job_t *jobs, float *workspace,
                             long long workspace_floats, int *sync, msr3d_stream_t stream);

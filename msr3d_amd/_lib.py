@@ -123,7 +123,6 @@ _SIGNATURES = {
                                _ptr, _c_int, _ptr],
     "msr3d_fp8_gemm_lowrank_acc": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int,
                                _ptr, _c_int, _ptr],
-    "msr3d_wgrad_split_halves": [_c_int, _ptr, _ptr, _c_int, _ptr, ctypes.c_longlong, _ptr, _ptr],
     "msr3d_wgrad_split_mixed": [_c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, ctypes.c_longlong, _ptr, _ptr],
     "msr3d_wgrad_stream": [_c_int, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, ctypes.c_longlong, _ptr, _ptr],
     "msr3d_wgrad_rows_split": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr,
@@ -271,10 +270,10 @@ _lib = None
 
 def exported_symbols():
     """Every symbol include/msr3d_hip.h declares (checked by the CPU test-suite)."""
-    return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form", "msr3d_attn_fwd_form"] + list(_SIGNATURES)
+    return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 31       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 32       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():
@@ -299,8 +298,6 @@ def load():
     lib.msr3d_sqdist_contract.restype = _c_int
     lib.msr3d_wgrad_form.restype = _c_int
     lib.msr3d_wgrad_form.argtypes = [_c_int]
-    lib.msr3d_attn_fwd_form.restype = _c_int
-    lib.msr3d_attn_fwd_form.argtypes = [_c_int]
     lib.msr3d_status_string.restype = ctypes.c_char_p
     lib.msr3d_status_string.argtypes = [_c_int]
     for name, argtypes in _SIGNATURES.items():
@@ -382,8 +379,8 @@ def load_split2():
 
 
 _lib_bf16 = None
-_BF16_ENTRIES = ("msr3d_scene_block", "msr3d_wgrad_split", "msr3d_wgrad_split_colsum", "msr3d_wgrad_split_halves",
-                 "msr3d_wgrad_split_mixed", "msr3d_wgrad_stream")
+_BF16_ENTRIES = ("msr3d_scene_block", "msr3d_wgrad_split", "msr3d_wgrad_split_colsum", "msr3d_wgrad_split_mixed",
+                 "msr3d_wgrad_stream")
 
 
 def load_bf16():
@@ -405,8 +402,6 @@ def load_bf16():
                 f"{ABI_VERSION} (include/msr3d_hip.h). Rebuild it with `python -m msr3d_amd.build`.")
         lib.msr3d_wgrad_form.restype = _c_int
         lib.msr3d_wgrad_form.argtypes = [_c_int]
-        lib.msr3d_attn_fwd_form.restype = _c_int
-        lib.msr3d_attn_fwd_form.argtypes = [_c_int]
         for name in _BF16_ENTRIES:
             fn = getattr(lib, name)
             fn.argtypes = _SIGNATURES[name]

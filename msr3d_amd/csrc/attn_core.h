@@ -173,51 +173,6 @@ __device__ __forceinline__ void load_probs_tile(const float *__restrict__ probs_
   }
 }
 
-// The same two tiles fetched into REGISTERS first (the fused blocks issue these loads ahead of a matrix
-// product whose operand still occupies the LDS they are headed for) and stored later.  64-token tile,
-// 256 threads; `vec` (16-byte aligned source, element count % 4 == 0) is the caller's to check.
-constexpr int kPlocRegs = 64 * 64 * SD / 4 / 256;       // 20 float4 per thread
-__device__ __forceinline__ void ploc_fetch(const float *__restrict__ src, int n4, float4 (&v)[kPlocRegs]) {
-#pragma unroll
-  for (int k = 0; k < kPlocRegs; ++k) {
-    const int e = threadIdx.x + 256 * k;
-    v[k] = e < n4 ? reinterpret_cast<const float4 *>(src)[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-__device__ __forceinline__ void ploc_store(float *spl, int n4, const float4 (&v)[kPlocRegs]) {
-#pragma unroll
-  for (int k = 0; k < kPlocRegs; ++k) {
-    const int e = threadIdx.x + 256 * k;
-    if (e < n4) reinterpret_cast<float4 *>(spl)[e] = v[k];
-  }
-}
-constexpr int kProbRegs = 64 * 64 / 4 / 256;            // 4 float4 per thread
-__device__ __forceinline__ void probs_fetch(const float *__restrict__ probs_bh, int L, float4 (&v)[kProbRegs]) {
-  const int n4 = (L * L) >> 2;
-#pragma unroll
-  for (int k = 0; k < kProbRegs; ++k) {
-    const int e = threadIdx.x + 256 * k;
-    v[k] = e < n4 ? reinterpret_cast<const float4 *>(probs_bh)[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-// L % 4 == 0: a float4 never straddles a row; [64][68] tile, zero outside (L, L)
-__device__ __forceinline__ void probs_store(float *sp, int L, const float4 (&v)[kProbRegs]) {
-  constexpr int LDP = 64 + 4;
-  const int n4 = (L * L) >> 2;
-#pragma unroll
-  for (int k = 0; k < kProbRegs; ++k) {
-    const int e = threadIdx.x + 256 * k;
-    if (e < n4) {
-      const int idx = 4 * e, row = idx / L, col = idx - row * L;
-      *reinterpret_cast<float4 *>(sp + row * LDP + col) = v[k];
-    }
-  }
-  for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-    const int row = e >> 6, col = e & 63;
-    if (row >= L || col >= L) sp[row * LDP + col] = 0.f;
-  }
-}
-
 struct RowCond { float bias, w[SD]; };
 
 // `cond0`: the (bias, w[5]) sextet of row 0 of this (scene, head); rows are `ldc` floats apart
@@ -252,8 +207,7 @@ __device__ __forceinline__ void attn_fwd_core(int L, const float *sq, const floa
   constexpr float kPScale = (MMA == MSR3D_MMA_FP8) ? 256.f : 1.f;   // P into e4m3's normal range
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4, row0 = wave * 16;
-  // a workgroup may hold more waves than query tiles (the fused block with two waves per SIMD): the extra waves only
-  // keep the barrier company
+  // a workgroup may hold more waves than query tiles: the extra waves only keep the barrier company
   const bool act = wave < NT;
   if (act) {
   f32x4 acc[NT];
@@ -327,8 +281,7 @@ __device__ __forceinline__ void attn_fwd_core(int L, const float *sq, const floa
 // the accumulator layout (row = 16 wave + 4 g + r, col = 16 rn + i; dq / dk still to be divided by
 // sqrt(dh)) and writes the (bias, w[5]) gradients of each row to dcond0 + row * lddc (lane i == 0).
 // =================================================================================
-// TR: dq / dk / dv returned TRANSPOSED per tile (strip_mma's SWAP): element (row = 16 wave + i, col = 16 rn + 4 g + r).
-template <int LT, int MMA, bool TR = false>
+template <int LT, int MMA>
 __device__ __forceinline__ void attn_bwd_core(int L, const float *sq, const float *sk, const float *sv,
                                               const float *sdo, float *sp, const float *plb, const float *cond0,
                                               int ldc, const unsigned char *pad_b, float *dcond0, int lddc,
@@ -344,7 +297,7 @@ __device__ __forceinline__ void attn_bwd_core(int L, const float *sq, const floa
   // dv = P^T dctx (rows = keys) while P is still intact
   ov[0] = f32x4{0.f, 0.f, 0.f, 0.f};
   ov[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  strip_mma<MMA, 2, LT, false, false, TR>(sp, LDP, sdo, LD32, row0, ov, lane);
+  strip_mma<MMA, 2, LT, false, false>(sp, LDP, sdo, LD32, row0, ov, lane);
   __syncthreads();                       // every wave is done reading P as a matrix operand
 
   bool keyok[NT];
@@ -401,8 +354,8 @@ __device__ __forceinline__ void attn_bwd_core(int L, const float *sq, const floa
     oq[rn] = f32x4{0.f, 0.f, 0.f, 0.f};
     ok[rn] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  strip_mma<MMA, 2, LT, true, false, TR>(sp, LDP, sk, LD32, row0, oq, lane);
-  strip_mma<MMA, 2, LT, false, false, TR>(sp, LDP, sq, LD32, row0, ok, lane);
+  strip_mma<MMA, 2, LT, true, false>(sp, LDP, sk, LD32, row0, oq, lane);
+  strip_mma<MMA, 2, LT, false, false>(sp, LDP, sq, LD32, row0, ok, lane);
 }
 
 }  // namespace msr3d_attn

@@ -12,16 +12,16 @@
 //                                                in slab order, by the next msr3d_scene_rows launch
 //
 // with the middle = spatial attention of one head (attn_core.h), GELU + dropout, or their backward.
-// One workgroup (4 waves) per (scene, slice): 128 workgroups for the attention blocks, 256 for the
-// feed-forward blocks.  The (tokens x 2048) activation, q / k / v and the context vectors never go
+// One workgroup per (scene, slice) -- the attention forward: two, one per half of the query rows -- of
+// eight waves; four for the linear blocks.  The (tokens x 2048) activation, q / k / v and the context vectors never go
 // through HBM between the two products (they are written once, as side outputs for the backward).
 //
 // Matrix products: six v_mfma_f32_16x16x32_bf16 per block of products on exactly-split operands
 // (split_mma.h).  `mid` is split by product 1's epilogue into fragment-order planes in LDS; the weights
 // arrive pre-split and fragment-packed (msr3d_split_pack, once per optimiser step) through a buffer
 // descriptor and a register ring four pieces deep, so there is no LDS staging of weights and no barrier
-// inside a product.  Waves are laid out 1 x 4: each owns all 64 rows and a quarter of the columns, so a
-// weight fragment is fetched once per workgroup.
+// inside a product.  In scene_block_kernel the waves are laid out 1 x NW: each owns all 64 rows and its share
+// of the columns, so a weight fragment is fetched once per workgroup.
 //
 // Why partial slabs and not atomics: scene_rows.hip.
 //
@@ -35,8 +35,6 @@
 // (MSR3D_FFN_SCENE_XCD=1 at build time: all sixteen slices' weights, 6.3 MB, past every 4 MB L2) is neutral on the day's
 // fast boxes and 14 us a step slower on the others: off.
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
 
 #include "../../include/msr3d_hip.h"
 #include "attn_core.h"
@@ -123,22 +121,6 @@ __device__ __forceinline__ void stage_planes(const unsigned short *__restrict__ 
   }
 }
 
-// stage_planes in two steps (256 threads): the loads, and -- after the caller has issued other loads behind them -- the
-// LDS stores
-__device__ __forceinline__ void planes_fetch(const unsigned short *__restrict__ xp, int b, uint4 (&v)[24]) {
-  const uint4 *src = reinterpret_cast<const uint4 *>(xp + (size_t)b * 3 * TM * KD);
-#pragma unroll
-  for (int k = 0; k < 8 * kPlanes; ++k) v[k] = src[threadIdx.x + 256 * k];
-}
-__device__ __forceinline__ void planes_store(unsigned short *xs, const uint4 (&v)[24]) {
-#pragma unroll
-  for (int k = 0; k < 8 * kPlanes; ++k) {
-    const int q = threadIdx.x + 256 * k;
-    const int plane = q >> 11, row = (q >> 5) & 63, c8 = q & 31;
-    *reinterpret_cast<uint4 *>(xs + plane * PLANE + row * PITCH + c8 * 8) = v[k];
-  }
-}
-
 __device__ __forceinline__ void stage_f32(const float *__restrict__ a0, int lda, int col0, unsigned short *xs,
                                           int row_base, int L) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -206,33 +188,23 @@ __device__ __forceinline__ float4 slab4_load(const Slab4 &s, int e) {
 
 // LDS carve-up behind the ROWS planes, by kind
 constexpr int kTile = TM * LD32 * 4;                       // one [64][36] fp32 head tile: 9,216 B
-constexpr int kAttnFwdAux = 3 * kTile + 2048 + 4 * 3 * 1024;          // q k v | cond [64][8] | ctx FRAG (1 slab)
 constexpr int kAttnBwdAux = 4 * kTile + 2048 + 2048;                   // q k v do | cond | dcond
 
 template <int KIND>
 constexpr int lds_bytes() {
-  return KIND == MSR3D_BLK_ATTN_FWD ? XS_BYTES + kAttnFwdAux
-       : KIND == MSR3D_BLK_ATTN_BWD ? XS_BYTES + kAttnBwdAux
-       : (KIND == MSR3D_BLK_FFN_FWD || KIND == MSR3D_BLK_FFN_BWD) ? XS_BYTES + MID_BYTES
-       : XS_BYTES;
+  return (KIND == MSR3D_BLK_FFN_FWD || KIND == MSR3D_BLK_FFN_BWD) ? XS_BYTES + MID_BYTES : XS_BYTES;
 }
 
-// NW: waves per workgroup.  8 (two per SIMD: one wave alone issues at most 44 % of a SIMD's VALU rate,
-// profiles/r05_hw_probes.txt) for the attention forward and the feed-forward blocks -- each wave then owns half the
-// column tiles -- 4 for the rest; MSR3D_ATTN_FWD_WAVES=4 / MSR3D_FFN_WAVES=4 restore four.
-template <int KIND, int NW = 4>
+// The feed-forward and the linear blocks (the attention blocks have kernels of their own below).  NW: waves per
+// workgroup.  8 (two per SIMD: one wave alone issues at most 44 % of a SIMD's VALU rate, profiles/r05_hw_probes.txt) for
+// the feed-forward blocks -- each wave then owns half the column tiles -- 4 for the linear ones.
+template <int KIND, int NW>
 __global__ __launch_bounds__(64 * NW) void scene_block_kernel(const SB p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned short *xs = reinterpret_cast<unsigned short *>(smem);
   unsigned char *aux = smem + XS_BYTES;
   // (rows_total > 0: row tiles that ignore scene boundaries -- tile b holds rows [b L, min((b + 1) L, rows_total)))
   int slice = blockIdx.x, b = blockIdx.y;
-#if MSR3D_ATTN_SCENE_XCD
-  if ((KIND == MSR3D_BLK_ATTN_FWD || KIND == MSR3D_BLK_ATTN_BWD) && gridDim.x == 8 && (gridDim.y & 7) == 0) {
-    const int id = blockIdx.y * 8 + blockIdx.x, jj = id >> 3;   // (a scene's eight heads on ONE XCD: see the file's head)
-    b = (id & 7) + 8 * (jj >> 3); slice = jj & 7;
-  }
-#endif
 #if MSR3D_FFN_SCENE_XCD
   if ((KIND == MSR3D_BLK_FFN_FWD || KIND == MSR3D_BLK_FFN_BWD) && gridDim.x == 16 && (gridDim.y & 7) == 0 && p.rows_total == 0) {
     const int id = blockIdx.y * 16 + blockIdx.x, jj = id >> 3;
@@ -247,21 +219,16 @@ __global__ __launch_bounds__(64 * NW) void scene_block_kernel(const SB p) {
   float *const slab = p.part + (size_t)slice * p.part_stride;
 
   // ---- product 1's stream: the first pieces fly under the prologue ----
-  constexpr int RN1 = (KIND == MSR3D_BLK_LINEAR || KIND == MSR3D_BLK_LINEAR_KSPLIT) ? 4
-                    : (KIND == MSR3D_BLK_ATTN_BWD || NW == 8) ? 1 : 2;
+  // column tiles per wave: 64 of a linear block's 256 columns, 128 / NW of a feed-forward slice's 128
+  constexpr int RN1 = (KIND == MSR3D_BLK_LINEAR || KIND == MSR3D_BLK_LINEAR_KSPLIT) ? 4 : 8 / NW;
   constexpr int KS1 = KD / 32;
   WStream w1;
-  if (KIND == MSR3D_BLK_ATTN_FWD)          // per head: [8 slabs][8 tiles]: q q k k v v cond -
-    w1 = make_wstream(p.w1 + (size_t)slice * (KS1 * 8 * kPieceBytes / 2), KS1 * 8 * kPieceBytes, 8, 0,
-                      NW == 8 ? wave : 2 * wave, lane);
-  else if (KIND == MSR3D_BLK_ATTN_BWD)     // Wfc as [k = fc row][n = ctx column]: [8 slabs][16 tiles], tiles 2 h, 2 h + 1
-    w1 = make_wstream(p.w1, p.w1_bytes, 16, 0, 2 * slice + (wave & 1), lane);
-  else if (KIND == MSR3D_BLK_LINEAR)       // [8 slabs][N / 16 tiles]
+  if (KIND == MSR3D_BLK_LINEAR)            // [8 slabs][N / 16 tiles]
     w1 = make_wstream(p.w1, p.w1_bytes, p.N / 16, 0, 16 * slice + 4 * wave, lane);
   else if (KIND == MSR3D_BLK_LINEAR_KSPLIT)   // [K / 32 slabs][16 tiles]
     w1 = make_wstream(p.w1, p.w1_bytes, 16, KS1 * slice, 4 * wave, lane);
   else                                     // FFN: [8 slabs][ff / 16 tiles], this slice's 8 tiles
-    w1 = make_wstream(p.w1, p.w1_bytes, p.ff / 16, 0, 8 * slice + (8 / NW) * wave, lane);
+    w1 = make_wstream(p.w1, p.w1_bytes, p.ff / 16, 0, 8 * slice + RN1 * wave, lane);
   SB_STAMP(0);
   WPiece ring1[RING];
   preload_wring<RN1, RING>(ring1, w1);
@@ -306,7 +273,7 @@ __global__ __launch_bounds__(64 * NW) void scene_block_kernel(const SB p) {
     // ------------------------------------------------------------------ feed-forward block
     constexpr bool FWD = KIND == MSR3D_BLK_FFN_FWD;
     const int ff = p.ff;
-    // NW = 4: a wave owns 32 of the slice's 128 middle columns and 64 of product 2's 256; NW = 8: 16 and 32
+    // a wave owns 128 / NW of the slice's 128 middle columns and 256 / NW of product 2's 256
     constexpr int RN2 = 16 / NW, RING2 = RING;         // (product 2: 4 slabs x RN2 pieces >= RING)
     const int lc0 = 16 * RN1 * wave + 4 * g;           // + 16 rn: the lane's four middle columns inside the slice
     const int hc0 = 128 * slice + lc0;
@@ -380,203 +347,6 @@ __global__ __launch_bounds__(64 * NW) void scene_block_kernel(const SB p) {
     gemm_split3<true, RN2, 4, 4, RING2>(xm, 0, w2, acc2, ring2);
     SB_STAMP(6);
     store_partials<RN2>(acc2, slab, row_base, L, 16 * RN2 * wave, lane);
-  } else if constexpr (KIND == MSR3D_BLK_ATTN_FWD) {
-    // ------------------------------------------------------------------ attention block, forward
-    const int h = slice, H = p.H, ldq = p.ldq;
-    float *sq = reinterpret_cast<float *>(aux), *sk = sq + TM * LD32, *sv = sk + TM * LD32;
-    float *scond = sv + TM * LD32;                                  // [64][8]
-    unsigned char *ctxp = reinterpret_cast<unsigned char *>(scond + TM * 8);   // FRAG, 1 slab x 4 row tiles
-    // product 2's stream: Wfc [8 slabs][16 tiles], slab h
-    constexpr int RN2 = 16 / NW, RING2 = RN2 < RING ? RN2 : RING;
-    const WStream w2 = make_wstream(p.w2, p.w2_bytes, 16, h, RN2 * wave, lane);
-    // the scene's pairwise slab is headed for the LDS the planes occupy: fetched into registers now (threads 0..255)
-    const float *plsrc = p.ploc + (size_t)b * L * L * SD;
-    const int pn = L * L * SD;
-    const Slab4 pls = make_slab4(plsrc, pn);          // (16-byte vectors at any alignment: L = 61)
-    const bool plt = NW == 4 || tid < 256;
-    float4 plv[msr3d_attn::kPlocRegs];
-    if (plt) {
-#pragma unroll
-      for (int k = 0; k < msr3d_attn::kPlocRegs; ++k) plv[k] = slab4_load(pls, tid + 256 * k);
-    }
-    f32x4 acc[RN1][4];
-    zero_acc3(acc);
-    gemm_split3<true, RN1, 4, KS1, RING>(xr, 0, w1, acc, ring1);
-    SB_STAMP(3);
-    WPiece ring2[RING2];
-    preload_wring<RN2, RING2>(ring2, w2);
-    // the head's column tiles: q q k k v v cond -.  NW = 4: wave 0 / 1 / 2 the head's q / k / v (32 columns each),
-    // wave 3 cond; NW = 8: one tile a wave
-    constexpr int TPW = 8 / NW;                                       // column tiles per wave
-    const int which = (TPW * wave) >> 1;                              // 0 q, 1 k, 2 v, 3 cond
-    if (which < 3) {
-      float *tile = sq + which * TM * LD32;
-#pragma unroll
-      for (int rn = 0; rn < RN1; ++rn) {
-        const int c = 16 * ((TPW * wave + rn) & 1) + 4 * g;
-        const float4 bv = ld4(p.bias1 + which * KD + h * DH + c);     // bias of the packed [q | k | v | cond] rows
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          const int row = 16 * mt + j;
-          const bool ok = row < L;
-          const float4 v = ok ? make_float4(acc[rn][mt][0] + bv.x, acc[rn][mt][1] + bv.y, acc[rn][mt][2] + bv.z,
-                                            acc[rn][mt][3] + bv.w)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
-          st4(tile + row * LD32 + c, v);
-          if (ok) st4(p.qkvc + (size_t)(row_base + row) * ldq + which * KD + h * DH + c, v);
-        }
-      }
-    } else if (TPW * wave == 6) {
-      float b4[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) b4[r] = 4 * g + r < SD + 1 ? p.bias1[3 * KD + h * (SD + 1) + 4 * g + r] : 0.f;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int row = 16 * mt + j;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = 4 * g + r;
-          const float v = row < L ? acc[0][mt][r] + b4[r] : 0.f;
-          if (c < 8) scond[row * 8 + c] = c < SD + 1 ? v : 0.f;
-          if (c < SD + 1 && row < L) p.qkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] = v;
-        }
-      }
-    }
-    SB_STAMP(4);
-    __syncthreads();                       // every wave is done with the ROWS planes; q / k / v / cond visible
-    float *sp = reinterpret_cast<float *>(xs);                      // P [64][68], then the pairwise slab
-    const float *plb = sp + TM * (TM + 4) + pls.mis;
-    if (plt) {
-#pragma unroll
-      for (int k = 0; k < msr3d_attn::kPlocRegs; ++k) {
-        const int e = tid + 256 * k;
-        if (e < pls.n4) reinterpret_cast<float4 *>(sp + TM * (TM + 4))[e] = plv[k];
-      }
-    }
-    __syncthreads();
-    SB_STAMP(5);
-    f32x4 o[2];
-    msr3d_attn::attn_fwd_core<TM, kCoreMma>(L, sq, sk, sv, sp, plb, scond, 8, p.pad + (size_t)b * L,
-                                                 p.probs ? p.probs + ((size_t)b * H + h) * L * L : nullptr, o);
-    // ctx_h: side output + product 2's operand (FRAG planes, one slab; row tile = wave)
-    if (wave < 4) {
-#pragma unroll
-      for (int rn = 0; rn < 2; ++rn)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int rr = 4 * g + r, row = 16 * wave + rr, kk = 16 * rn + j;
-          const float v = row < L ? o[rn][r] : 0.f;
-          if (row < L) p.ctx[(size_t)(row_base + row) * KD + h * DH + kk] = v;
-          unsigned short pl[3];
-          sm_split1(v, pl);
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            *reinterpret_cast<unsigned short *>(ctxp + (((wave * 3 + k) * 64 + rr + 16 * (kk >> 3)) * 16 + (kk & 7) * 2)) = pl[k];
-        }
-    }
-    SB_STAMP(6);
-    __syncthreads();
-    f32x4 acc2[RN2][4];
-    zero_acc3(acc2);
-    const XFrag<4> xm{reinterpret_cast<const unsigned short *>(ctxp) + lane * 8};
-    gemm_split3<true, RN2, 4, 1, RING2>(xm, 0, w2, acc2, ring2);
-    SB_STAMP(7);
-    store_partials<RN2>(acc2, slab, row_base, L, 16 * RN2 * wave, lane);
-  } else {
-    // ------------------------------------------------------------------ attention block, backward
-    const int h = slice, H = p.H, ldq = p.ldq;
-    float *sq = reinterpret_cast<float *>(aux), *sk = sq + TM * LD32, *sv = sk + TM * LD32, *sdo = sv + TM * LD32;
-    float *scond = sdo + TM * LD32, *sdc = scond + TM * 8;
-    // product 2's stream: the head's gathered rows of W_qkvc as [k = 128 head columns][n = 256]: [4 slabs][16 tiles]
-    const WStream w2 = make_wstream(p.w2 + (size_t)h * (4 * 16 * kPieceBytes / 2), 4 * 16 * kPieceBytes, 16, 0, 4 * wave, lane);
-    // the head's saved q, k, v, cond
-    msr3d_attn::load_head_tile<TM>(p.qkvc, ldq, b, h, L, sq);
-    msr3d_attn::load_head_tile<TM>(p.qkvc + KD, ldq, b, h, L, sk);
-    msr3d_attn::load_head_tile<TM>(p.qkvc + 2 * KD, ldq, b, h, L, sv);
-    for (int e = tid; e < TM * 8; e += 256) {
-      const int row = e >> 3, c = e & 7;
-      scond[e] = (row < L && c < SD + 1) ? p.qkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] : 0.f;
-    }
-    const float *plsrc = p.ploc + (size_t)b * L * L * SD, *prsrc = p.probs + ((size_t)b * H + h) * L * L;
-    const int pn = L * L * SD;
-    const bool pvec = (reinterpret_cast<uintptr_t>(plsrc) & 15u) == 0 && (pn & 3) == 0;
-    const bool qvec = (reinterpret_cast<uintptr_t>(prsrc) & 15u) == 0 && (L & 3) == 0;
-    float4 plv[msr3d_attn::kPlocRegs], prv[msr3d_attn::kProbRegs];
-    if (pvec) msr3d_attn::ploc_fetch(plsrc, pn >> 2, plv);
-    if (qvec) msr3d_attn::probs_fetch(prsrc, L, prv);
-    // d ctx_h = d_fc Wfc[:, 32 h : 32 h + 32]: wave (wr, wc) owns row tiles 2 wr, 2 wr + 1 and column tile wc
-    f32x4 acc[1][2];
-    zero_acc3(acc);
-    gemm_split3<true, 1, 2, KS1, RING>(xr, 2 * (wave >> 1), w1, acc, ring1);
-    SB_STAMP(3);
-    WPiece ring2[RING];
-    preload_wring<4, RING>(ring2, w2);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const int row = 16 * (2 * (wave >> 1) + mt) + j;
-      const float4 v = row < L ? make_float4(acc[0][mt][0], acc[0][mt][1], acc[0][mt][2], acc[0][mt][3])
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
-      st4(sdo + row * LD32 + 16 * (wave & 1) + 4 * g, v);
-    }
-    __syncthreads();                       // planes free; q / k / v / cond / d ctx visible
-    float *sp = reinterpret_cast<float *>(xs);
-    if (qvec) msr3d_attn::probs_store(sp, L, prv);
-    else msr3d_attn::load_probs_tile<TM>(prsrc, L, sp);
-    const float *plb = sp + TM * (TM + 4);
-    if (pvec) msr3d_attn::ploc_store(sp + TM * (TM + 4), pn >> 2, plv);
-    else plb = msr3d_attn::stage_ploc<TM>(p.ploc, b, L, sp + TM * (TM + 4));
-    __syncthreads();
-    SB_STAMP(5);
-    f32x4 oq[2], ok[2], ov[2];
-    msr3d_attn::attn_bwd_core<TM, kCoreMma>(L, sq, sk, sv, sdo, sp, plb, scond, 8, p.pad + (size_t)b * L, sdc, 8,
-                                                 oq, ok, ov);
-    SB_STAMP(6);
-    // every wave is past the core's last barrier: the pairwise slab is dead, product 2's operand
-    // (FRAG planes, 4 slabs: [dq | dk | dv | dcond, 0]) goes on top of it
-    unsigned char *mid = reinterpret_cast<unsigned char *>(sp + TM * (TM + 4));
-#pragma unroll
-    for (int rn = 0; rn < 2; ++rn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = 4 * g + r, row = 16 * wave + rr, kk = 16 * rn + j;
-        const bool okr = row < L;
-        const float v3[3] = {okr ? oq[rn][r] * kInvSqrtDh : 0.f, okr ? ok[rn][r] * kInvSqrtDh : 0.f, okr ? ov[rn][r] : 0.f};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          if (okr) p.dqkvc[(size_t)(row_base + row) * ldq + a * KD + h * DH + kk] = v3[a];
-          unsigned short pl[3];
-          sm_split1(v3[a], pl);
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            *reinterpret_cast<unsigned short *>(mid + ((((a * 4 + wave) * 3 + k) * 64 + rr + 16 * (kk >> 3)) * 16 + (kk & 7) * 2)) = pl[k];
-        }
-      }
-    if (tid < TM) {                        // slab 3 of row `tid`: the six cond gradients, zeros behind them
-      const int row = tid;
-      float dc[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) dc[c] = (row < L && c < SD + 1) ? sdc[row * 8 + c] : 0.f;
-      if (row < L) {
-#pragma unroll
-        for (int c = 0; c < SD + 1; ++c) p.dqkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] = dc[c];
-      }
-      uint4 pl[3];
-      sm_split8(dc, pl);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        unsigned char *d = mid + (((3 * 4 + (row >> 4)) * 3 + k) * 64 + (row & 15)) * 16;
-        *reinterpret_cast<uint4 *>(d) = pl[k];
-#pragma unroll
-        for (int gg = 1; gg < 4; ++gg) *reinterpret_cast<uint4 *>(d + gg * 256) = make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-    __syncthreads();
-    f32x4 acc2[4][4];
-    zero_acc3(acc2);
-    const XFrag<4> xm{reinterpret_cast<const unsigned short *>(mid) + lane * 8};
-    gemm_split3<true, 4, 4, 4, RING>(xm, 0, w2, acc2, ring2);
-    SB_STAMP(7);
-    store_partials<4>(acc2, slab, row_base, L, 64 * wave, lane);
   }
   SB_STAMP(8);
 }
@@ -838,183 +608,19 @@ __global__ __launch_bounds__(512) void scene_attn_fwd2_kernel(const SB p) {
 }
 
 // =====================================================================================================
-// Attention block, backward (one workgroup of four waves per (scene, head), as scene_block_kernel<ATTN_BWD> was), with
-// ALL of the block's inputs crossing the fabric together: the head's saved q / k / v / cond and probabilities are asked
-// for with the planes (they used to be fetched, one dependent round trip after another, once the planes had arrived:
-// 13 k cycles in front of an 8-piece product), all eight weight pieces of product 1 sit in registers before the pairwise
-// slab's 72 KB are requested (loads complete in order), and the core returns dq / dk / dv transposed per tile
-// (attn_core.h: strip_mma's SWAP) so that the side outputs are 16-byte stores and product 2's operand 8-byte LDS stores.
-// MSR3D_ATTN_BWD_V2=0 restores scene_block_kernel<ATTN_BWD>.
-// =====================================================================================================
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void scene_attn_bwd2_kernel(const SB p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned short *xs = reinterpret_cast<unsigned short *>(smem);
-  unsigned char *aux = smem + XS_BYTES;
-  const int slice = blockIdx.x, b = blockIdx.y, L = p.L;
-  const int row_base = b * L;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, g = lane >> 4;
-  float *const slab = p.part + (size_t)slice * p.part_stride;
-  constexpr int KS1 = KD / 32;
-  {
-    const int h = slice, H = p.H, ldq = p.ldq;
-    float *sq = reinterpret_cast<float *>(aux), *sk = sq + TM * LD32, *sv = sk + TM * LD32, *sdo = sv + TM * LD32;
-    float *scond = sdo + TM * LD32, *sdc = scond + TM * 8;
-    // Wfc as [k = fc row][n = ctx column]: [8 slabs][16 tiles], tiles 2 h, 2 h + 1
-    const WStream w1 = make_wstream(p.w1, p.w1_bytes, 16, 0, 2 * slice + (wave & 1), lane);
-    SB_STAMP(0);
-    WPiece ring1[8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) load_wpiece(ring1[q], w1, q, 0);
-    uint4 xv[24];
-    planes_fetch(p.xp, b, xv);
-    // saved q / k / v (two float4 a thread and tile), cond, probabilities
-    float4 tq[6];
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int e = tid + 256 * k, row = e >> 3, c4 = (e & 7) * 4;
-        tq[2 * t + k] = row < L ? ld4(p.qkvc + (size_t)(row_base + row) * ldq + t * KD + h * DH + c4)
-                                : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    float tc[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int e = tid + 256 * k, row = e >> 3, c = e & 7;
-      tc[k] = (row < L && c < SD + 1) ? p.qkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] : 0.f;
-    }
-    const float *plsrc = p.ploc + (size_t)b * L * L * SD, *prsrc = p.probs + ((size_t)b * H + h) * L * L;
-    const int pn = L * L * SD;
-    const bool pvec = (reinterpret_cast<uintptr_t>(plsrc) & 15u) == 0 && (pn & 3) == 0;
-    const bool qvec = (reinterpret_cast<uintptr_t>(prsrc) & 15u) == 0 && (L & 3) == 0;
-    float4 plv[msr3d_attn::kPlocRegs], prv[msr3d_attn::kProbRegs];
-    if (qvec) msr3d_attn::probs_fetch(prsrc, L, prv);
-    {
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int e = tid + 256 * k, row = e >> 3, c4 = (e & 7) * 4;
-          st4(sq + t * TM * LD32 + row * LD32 + c4, tq[2 * t + k]);
-        }
-#pragma unroll
-      for (int k = 0; k < 2; ++k) scond[tid + 256 * k] = tc[k];
-      planes_store(xs, xv);
-    }
-    // the planes' registers are free: the rest of product 1's pieces, then the pairwise slab (consumed after product 1).
-    // (Their addresses pass through an empty asm so that no pass hoists these loads above the planes' stores.  No
-    //  sched_barrier in this prologue: with them the planes went to scratch, one serialised load at a time.)
-    {
-      WStream w1b = w1;
-      const float *plsrc2 = plsrc;
-      asm volatile("" : "+s"(w1b.soff), "+s"(plsrc2) : : "memory");
-#pragma unroll
-      for (int q = 4; q < 8; ++q) load_wpiece(ring1[q], w1b, q, 0);
-      if (pvec) msr3d_attn::ploc_fetch(plsrc2, pn >> 2, plv);
-    }
-    SB_STAMP(1);
-    __syncthreads();
-    SB_STAMP(2);
-    const XRows xr = make_xrows(xs, PITCH, TM, lane);
-    // ------------------------------------------------------------------ attention block, backward
-    // product 2's stream: the head's gathered rows of W_qkvc as [k = 128 head columns][n = 256]: [4 slabs][16 tiles]
-    const WStream w2 = make_wstream(p.w2 + (size_t)h * (4 * 16 * kPieceBytes / 2), 4 * 16 * kPieceBytes, 16, 0, 4 * wave, lane);
-    // d ctx_h = d_fc Wfc[:, 32 h : 32 h + 32]: wave (wr, wc) owns row tiles 2 wr, 2 wr + 1 and column tile wc
-    f32x4 acc[1][2];
-    zero_acc3(acc);
-    gemm_split3<true, 1, 2, KS1, 8>(xr, 2 * (wave >> 1), w1, acc, ring1);
-    SB_STAMP(3);
-    WPiece ring2[RING];
-    preload_wring<4, RING>(ring2, w2);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const int row = 16 * (2 * (wave >> 1) + mt) + j;
-      const float4 v = row < L ? make_float4(acc[0][mt][0], acc[0][mt][1], acc[0][mt][2], acc[0][mt][3])
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
-      st4(sdo + row * LD32 + 16 * (wave & 1) + 4 * g, v);
-    }
-    __syncthreads();                       // planes free; q / k / v / cond / d ctx visible
-    float *sp = reinterpret_cast<float *>(xs);
-    if (qvec) msr3d_attn::probs_store(sp, L, prv);
-    else msr3d_attn::load_probs_tile<TM>(prsrc, L, sp);
-    const float *plb = sp + TM * (TM + 4);
-    if (pvec) msr3d_attn::ploc_store(sp + TM * (TM + 4), pn >> 2, plv);
-    else plb = msr3d_attn::stage_ploc<TM>(p.ploc, b, L, sp + TM * (TM + 4));
-    __syncthreads();
-    SB_STAMP(5);
-    f32x4 oq[2], ok[2], ov[2];
-    msr3d_attn::attn_bwd_core<TM, kCoreMma, true>(L, sq, sk, sv, sdo, sp, plb, scond, 8, p.pad + (size_t)b * L, sdc, 8,
-                                                       oq, ok, ov);
-    SB_STAMP(6);
-    // every wave is past the core's last barrier: the pairwise slab is dead, product 2's operand
-    // (FRAG planes, 4 slabs: [dq | dk | dv | dcond, 0]) goes on top of it.  The core hands dq / dk / dv over transposed:
-    // a lane holds columns 16 rn + 4 g .. + 3 of row 16 wave + j -- one 16-byte side-output store and one 8-byte LDS
-    // store per plane (they were four 4-byte and twelve 2-byte stores per tile and operand: 11 k cycles of the block)
-    unsigned char *mid = reinterpret_cast<unsigned char *>(sp + TM * (TM + 4));
-    {
-      const int row = 16 * wave + j;
-      const bool okr = row < L;
-#pragma unroll
-      for (int rn = 0; rn < 2; ++rn)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const f32x4 &src = a == 0 ? oq[rn] : a == 1 ? ok[rn] : ov[rn];
-          const float sc = a < 2 ? kInvSqrtDh : 1.0f;
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = okr ? src[r] * sc : 0.f;
-          if (okr) st4(p.dqkvc + (size_t)(row_base + row) * ldq + a * KD + h * DH + 16 * rn + 4 * g, make_float4(v[0], v[1], v[2], v[3]));
-          uint2 pl[3];
-          sm_split4(v, pl);
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            *reinterpret_cast<uint2 *>(mid + frag_off4<4>(wave, j, 32 * a + 16 * rn + 4 * g, k)) = pl[k];
-        }
-    }
-    if (tid < TM) {                        // slab 3 of row `tid`: the six cond gradients, zeros behind them
-      const int row = tid;
-      float dc[8];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) dc[c] = (row < L && c < SD + 1) ? sdc[row * 8 + c] : 0.f;
-      if (row < L) {
-#pragma unroll
-        for (int c = 0; c < SD + 1; ++c) p.dqkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] = dc[c];
-      }
-      uint4 pl[3];
-      sm_split8(dc, pl);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        unsigned char *d = mid + (((3 * 4 + (row >> 4)) * 3 + k) * 64 + (row & 15)) * 16;
-        *reinterpret_cast<uint4 *>(d) = pl[k];
-#pragma unroll
-        for (int gg = 1; gg < 4; ++gg) *reinterpret_cast<uint4 *>(d + gg * 256) = make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-    __syncthreads();
-    f32x4 acc2[4][4];
-    zero_acc3(acc2);
-    const XFrag<4> xm{reinterpret_cast<const unsigned short *>(mid) + lane * 8};
-    gemm_split3<true, 4, 4, 4, RING>(xm, 0, w2, acc2, ring2);
-    SB_STAMP(7);
-    store_partials<4>(acc2, slab, row_base, L, 64 * wave, lane);
-  }
-  SB_STAMP(8);
-}
-
-// =====================================================================================================
-// Attention block, backward, EIGHT waves (two per SIMD) with the core's work split over all of them
-// (scene_attn_bwd2_kernel's four waves each carried 16 (query, key) pairs per lane through the softmax /
-// sigmoid backward: 14-15 k of the block's 47 k cycles).  Wave (t, kh): query / key tile t, key half kh.
-//   d P     16 queries x the half's 32 keys                      (was: x 64)
-//   d v     tile t's 16 keys x column half kh, over all queries   (was: x 32 columns)
+// Attention block, backward: one workgroup of EIGHT waves (two per SIMD) per (scene, head), with the core's work split
+// over all of them.  Wave (t, kh): query / key tile t, key half kh.
+//   d P     16 queries x the half's 32 keys
+//   d v     tile t's 16 keys x column half kh, over all queries
 //   softmax / sigmoid backward on 8 pairs per lane; the row's  sum_k p dP  and the six cond gradients are partial
 //           sums over a key half that meet through LDS in half order (deterministic)
 //   d q, d k  tile t's 16 rows x column half kh
-// Product 1 (d ctx) is one tile-unit per wave, product 2 two column tiles per wave.  Everything else as bwd2: inputs
-// requested up front, product 1's eight pieces in registers before the pairwise slab is asked for, transposed core
-// outputs.  MSR3D_ATTN_BWD=2 selects scene_attn_bwd2_kernel, =0 scene_block_kernel<ATTN_BWD>.
+// Product 1 (d ctx) is one tile-unit per wave, product 2 two column tiles per wave.  ALL of the block's inputs cross the
+// fabric together: the head's saved q / k / v / cond, the probabilities and the pairwise slab are asked for with the
+// planes (fetched one dependent round trip after another once the planes had arrived, they stood 13 k cycles in front of
+// an 8-piece product), all eight weight pieces of product 1 sit in registers before the product starts, and the core's
+// dq / dk / dv come out transposed per tile (attn_core.h: strip_mma's SWAP) so that the side outputs are 16-byte stores
+// and product 2's operand 8-byte LDS stores.
 // =====================================================================================================
 constexpr int kAttnBwd3Aux = kAttnBwdAux + 2 * 64 * 4 + 2 * 64 * 8 * 4;     // + row dots [2][64] + cond partials [2][64][8]
 constexpr int kAttnBwd3Lds = XS_BYTES + kAttnBwd3Aux;
@@ -1274,7 +880,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   SB_STAMP(8);
 }
 
-template <int KIND, int NW = 4>
+template <int KIND, int NW>
 int launch_block(const SB &p, int slices, hipStream_t s) {
   constexpr int lds = lds_bytes<KIND>();
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_block_kernel<KIND, NW>),
@@ -1362,26 +968,9 @@ __global__ __launch_bounds__(256) void split_pack_kernel(int njobs, const msr3d_
   }
 }
 
-// the attention forward block's form: -1 not chosen yet (environment at first use), 0 one workgroup per (scene, head),
-// 1 two (msr3d_attn_fwd_form)
-int g_attn_fwd_form = -1;
-bool attn_fwd_split() {
-  if (g_attn_fwd_form < 0) {
-    const char *v = getenv("MSR3D_ATTN_FWD_SPLIT");
-    g_attn_fwd_form = (v && v[0] == '0') ? 0 : 1;
-  }
-  return g_attn_fwd_form != 0;
-}
-
 }  // namespace
 
 extern "C" {
-
-int msr3d_attn_fwd_form(int form) {
-  if (form == 0 || form == 1) g_attn_fwd_form = form;
-  else if (form != -1) return MSR3D_EINVAL;
-  return attn_fwd_split() ? 1 : 0;
-}
 
 int msr3d_split_pack(int njobs, const msr3d_pack_job_t *jobs, const int *piece_prefix, int total_pieces,
                      msr3d_stream_t stream) {
@@ -1427,69 +1016,38 @@ int msr3d_scene_block(const msr3d_scene_block_t *pp, msr3d_stream_t stream) {
       if (p.H != 8 || !p.w2 || !p.qkvc || !p.ploc || !p.pad || !p.ctx || !p.bias1 || p.ldq % 4) return MSR3D_EINVAL;
       if (p.w1_bytes < 8u * 8u * 8u * kPieceBytes || p.w2_bytes < 8u * 16u * kPieceBytes) return MSR3D_EINVAL;
       {
-        // two workgroups per (scene, head), keys split over the core's eight waves (round 5): the library's default;
-        // MSR3D_ATTN_FWD_SPLIT=0 / msr3d_attn_fwd_form(0): one workgroup per (scene, head)
-        if (attn_fwd_split()) {
-          static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_fwd2_kernel),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kAttnFwd2Lds);
-          if (attr != hipSuccess) return (int)attr;
-          scene_attn_fwd2_kernel<<<dim3(16, p.B), 512, kAttnFwd2Lds, s>>>(p);
-          return (int)hipGetLastError();
-        }
-      }
-      {
-        // eight waves per workgroup (two per SIMD) by default: -6 us a step in three interleaved same-box runs
-        // (1.2421 -> 1.2362 ms); MSR3D_ATTN_FWD_WAVES=4 restores round 3's four
-        static const bool eight = [] { const char *v = getenv("MSR3D_ATTN_FWD_WAVES"); return !(v && v[0] == '4'); }();
-        return eight ? launch_block<MSR3D_BLK_ATTN_FWD, 8>(p, 8, s) : launch_block<MSR3D_BLK_ATTN_FWD>(p, 8, s);
+        // two workgroups per (scene, head), keys split over the core's eight waves
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_fwd2_kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kAttnFwd2Lds);
+        if (attr != hipSuccess) return (int)attr;
+        scene_attn_fwd2_kernel<<<dim3(16, p.B), 512, kAttnFwd2Lds, s>>>(p);
+        return (int)hipGetLastError();
       }
     case MSR3D_BLK_FFN_FWD:
     case MSR3D_BLK_FFN_BWD:
       if (p.ff <= 0 || p.ff % 128 || p.ff / 128 > 16 || !p.w2 || !p.pre || !p.h) return MSR3D_EINVAL;
       if (p.w1_bytes < (unsigned)(8 * (p.ff / 16)) * kPieceBytes || p.w2_bytes < (unsigned)((p.ff / 32) * 16) * kPieceBytes)
         return MSR3D_EINVAL;
-      {
-        // eight waves here too (round 5): -1.6 us a step over the six feed-forward blocks in three interleaved same-box
-        // pairs (0.9497 / 0.9502 / 0.9479 -> 0.9492 / 0.9484 / 0.9453 ms) -- the blocks wait on their weight pieces and
-        // planes, not on instruction issue; MSR3D_FFN_WAVES=4 restores four
-        static const bool eight = [] { const char *v = getenv("MSR3D_FFN_WAVES"); return !(v && v[0] == '4'); }();
-        if (eight)
-          return p.kind == MSR3D_BLK_FFN_FWD ? launch_block<MSR3D_BLK_FFN_FWD, 8>(p, p.ff / 128, s)
-                                             : launch_block<MSR3D_BLK_FFN_BWD, 8>(p, p.ff / 128, s);
-      }
-      return p.kind == MSR3D_BLK_FFN_FWD ? launch_block<MSR3D_BLK_FFN_FWD>(p, p.ff / 128, s)
-                                         : launch_block<MSR3D_BLK_FFN_BWD>(p, p.ff / 128, s);
+      // eight waves (two per SIMD); the four-wave form and what it measured: HISTORY.md
+      return p.kind == MSR3D_BLK_FFN_FWD ? launch_block<MSR3D_BLK_FFN_FWD, 8>(p, p.ff / 128, s)
+                                         : launch_block<MSR3D_BLK_FFN_BWD, 8>(p, p.ff / 128, s);
     case MSR3D_BLK_ATTN_BWD:
       if (p.H != 8 || !p.w2 || !p.qkvc || !p.dqkvc || !p.ploc || !p.pad || !p.probs || p.ldq % 4) return MSR3D_EINVAL;
       if (p.w1_bytes < 8u * 16u * kPieceBytes || p.w2_bytes < 8u * 4u * 16u * kPieceBytes) return MSR3D_EINVAL;
       {
-        // 3 (default): eight waves, the core split over all of them; 2: scene_attn_bwd2_kernel; 0: scene_block_kernel<ATTN_BWD>
-        static const int ver = [] { const char *v = getenv("MSR3D_ATTN_BWD"); return (v && v[0] >= '0' && v[0] <= '3') ? v[0] - '0' : 3; }();
-        if (ver == 3) {
-          static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd3_kernel),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kAttnBwd3Lds);
-          if (attr != hipSuccess) return (int)attr;
-          scene_attn_bwd3_kernel<<<dim3(8, p.B), 512, kAttnBwd3Lds, s>>>(p);
-          return (int)hipGetLastError();
-        }
-        static const bool v2 = [] { const char *v = getenv("MSR3D_ATTN_BWD_V2"); return !(v && v[0] == '0'); }();
-        if (v2 && ver != 0) {
-          static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd2_kernel),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                             lds_bytes<MSR3D_BLK_ATTN_BWD>());
-          if (attr != hipSuccess) return (int)attr;
-          scene_attn_bwd2_kernel<<<dim3(8, p.B), 256, lds_bytes<MSR3D_BLK_ATTN_BWD>(), s>>>(p);
-          return (int)hipGetLastError();
-        }
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd3_kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kAttnBwd3Lds);
+        if (attr != hipSuccess) return (int)attr;
+        scene_attn_bwd3_kernel<<<dim3(8, p.B), 512, kAttnBwd3Lds, s>>>(p);
+        return (int)hipGetLastError();
       }
-      return launch_block<MSR3D_BLK_ATTN_BWD>(p, 8, s);
     case MSR3D_BLK_LINEAR:
       if (p.N <= 0 || p.N % 256 || !p.C || p.ldc % 4 || p.w1_bytes < (unsigned)(8 * (p.N / 16)) * kPieceBytes) return MSR3D_EINVAL;
-      return launch_block<MSR3D_BLK_LINEAR>(p, p.N / 256, s);
+      return launch_block<MSR3D_BLK_LINEAR, 4>(p, p.N / 256, s);
     case MSR3D_BLK_LINEAR_KSPLIT:
       if (p.lda0 <= 0 || p.lda0 % 256 || p.lda0 / 256 > 20) return MSR3D_EINVAL;
       if (p.w1_bytes < (unsigned)((p.lda0 / 32) * 16) * kPieceBytes) return MSR3D_EINVAL;
-      return launch_block<MSR3D_BLK_LINEAR_KSPLIT>(p, p.lda0 / 256, s);
+      return launch_block<MSR3D_BLK_LINEAR_KSPLIT, 4>(p, p.lda0 / 256, s);
     default:
       return MSR3D_EINVAL;
   }

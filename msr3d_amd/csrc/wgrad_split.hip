@@ -66,8 +66,8 @@ __device__ __forceinline__ int frag_slot(int j, int g) { return (4 * (j & 3) + (
 // x <- max(gamma (x - mean) rstd + beta, 0) per column, applied by the loaders before the split (xpro = [gamma | beta |
 // mean | rstd], k_in floats each) -- the normalised activation is never written (hipops._BNReLULinear).
 constexpr int NMULT = 8, NLOAD = 8, NTHREADS = (NMULT + NLOAD) * 64;
-// HALVES (msr3d_wgrad_split_halves): a tile's reduction is cut in two units of whole slab pairs so that the ~1.4
-// tiles per CU of a step spread evenly (360 one-per-CU tiles = two rounds, the second 41 % full).  A unit takes a
+// HALVES: one of the two units of whole slab pairs that a tile's reduction is cut into (wgrad_mixed_kernel cuts the
+// tiles of a launch's partial round; the stream launch hands its cut tiles over without a flag).  A unit takes a
 // ticket when it STARTS: the first starter (role 0) parks its accumulators in the tile's workspace slot and raises a
 // flag, the second (role 1) adds  first-half + second-half  in that fixed order -- whichever of them it is -- onto dW:
 // bit-reproducible, no float atomics; the flag's owner is resident when anyone waits for it.
@@ -674,59 +674,14 @@ __global__ __launch_bounds__(PIPE ? NTHREADS_PIPE : NTHREADS) void wgrad_split_k
   else wgrad_tile<false>(pr, local / nkt, local % nkt, smem);
 }
 
-// The same tiles as wgrad_split_kernel, each as TWO units (gridDim.x = 2 x padded tiles): workgroups [0, T) hold the
-// first halves, [T, 2 T) the second halves -- T is a multiple of 8, so both halves of a tile run on one XCD
-// (workgroup b -> XCD b % 8: speed only) and the parked image travels through that XCD's L2.
-// sync: [T] tickets | [T] flags (all zero between launches); ws: T slots of kHalfSlot floats.
-__global__ __launch_bounds__(NTHREADS) void wgrad_halves_kernel(int nprob, const WP *__restrict__ probs,
-                                                                const int *__restrict__ prefix, float *__restrict__ ws,
-                                                                int *__restrict__ sync) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int role_s;
-  const int T = gridDim.x >> 1;
-  const int second = blockIdx.x >= T ? 1 : 0;
-  const int t = blockIdx.x - second * T;
-  int lo = 0, hi = nprob - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  const WP pr = probs[lo];
-  const int lb = t - prefix[lo], nb = prefix[lo + 1] - prefix[lo];
-  const int local = ((lb - pr.xcd_rot) & 7) * (nb >> 3) + (lb >> 3);
-  const int nkt = (pr.k_in + TK - 1) / TK;
-  if (local >= ((pr.n_out + TN - 1) / TN) * nkt) return;
-  const int nslab = ((pr.M + 63) >> 6) << 1;
-  const int cut = ((nslab >> 1) + 1) & ~1;            // whole slab pairs: 30 slabs -> 16 + 14
-  Half hf;
-  hf.second = second;
-  hf.s0 = second ? cut : 0;
-  hf.s1 = second ? nslab : cut;
-  hf.ws = ws + (size_t)t * kHalfSlot;
-  hf.flag = sync + T + t;
-  if (cut >= nslab) {                                  // a reduction of one slab pair is not cut
-    if (second) return;
-    hf.s1 = nslab;
-    hf.role = -1;
-  } else {
-    if (threadIdx.x == 0) {
-      const int k = __hip_atomic_fetch_add(sync + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (k == 1) __hip_atomic_store(sync + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (both tickets taken)
-      role_s = k;
-    }
-    __syncthreads();
-    hf.role = role_s;
-  }
-  wgrad_tile<false, false, false, true>(pr, local / nkt, local % nkt, smem, 0, 0, nullptr, hf);
-}
-
 // MIXED (round 5): the step's ~330 real tiles on 256 CUs are one full round and a second one that is 29 % full -- the
-// launch lasts two tile times.  Cutting EVERY tile in two (wgrad_halves_kernel) does not change that ratio and pays the
-// hand-over everywhere (measured slower).  Here only the tiles of the partial round are cut: workgroups [0, W) take whole
+// launch lasts two tile times.  Cutting EVERY tile in two does not change that ratio and pays the hand-over everywhere
+// (measured slower: HISTORY.md).  Here only the tiles of the partial round are cut: workgroups [0, W) take whole
 // tiles, [W, W + H) and [W + H, W + 2 H) the first and second halves of tiles W .. W + H - 1 (H = tiles - W, a multiple
-// of 8: both halves on one XCD), so the second round lasts half a tile time.  Same ticket protocol as above (the unit
-// that STARTS first parks, the second adds first + second in that order: bit-reproducible); workgroups past W + 2 H
-// run the column-sum jobs.  sync: [H] tickets | [H] flags, zero between launches; ws: H slots.
+// of 8: both halves on one XCD -- workgroup b runs on XCD b % 8 -- so the parked image travels through that XCD's L2),
+// and the second round lasts half a tile time.  The ticket protocol of `Half` above (the unit that STARTS first parks,
+// the second adds first + second in that order: bit-reproducible); workgroups past W + 2 H run the column-sum jobs.
+// sync: [H] tickets | [H] flags, zero between launches; ws: H slots of kHalfSlot floats.
 template <bool PIPE>
 __global__ __launch_bounds__(PIPE ? NTHREADS_PIPE : NTHREADS) void wgrad_mixed_kernel(int nprob, const WP *__restrict__ probs,
                                                                const int *__restrict__ prefix, int tiles, int W,
@@ -977,21 +932,6 @@ extern "C" int msr3d_wgrad_split_colsum(int n, const msr3d_wgrad_problem_t *prob
   if ((n == 0 || total_tiles == 0) && n_jobs == 0) return 0;
   if ((total_tiles > 0 && (!problems || !tile_prefix)) || (n_jobs > 0 && !jobs)) return MSR3D_EINVAL;
   return launch_split(n, problems, tile_prefix, total_tiles, n_jobs, jobs, (hipStream_t)stream);
-}
-
-extern "C" int msr3d_wgrad_split_halves(int n, const msr3d_wgrad_problem_t *problems, const int *tile_prefix,
-                                        int total_tiles, float *workspace, long long workspace_floats, int *sync,
-                                        msr3d_stream_t stream) {
-  if (n < 0 || total_tiles < 0) return MSR3D_EINVAL;
-  if (n == 0 || total_tiles == 0) return 0;
-  if (!problems || !tile_prefix || !workspace || !sync || (total_tiles & 7)) return MSR3D_EINVAL;
-  if (workspace_floats < (long long)total_tiles * MSR3D_WGRAD_HALF_SLOT_FLOATS) return MSR3D_EINVAL;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_halves_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  if (attr != hipSuccess) return (int)attr;
-  wgrad_halves_kernel<<<2 * total_tiles, NTHREADS, LDS_BYTES, (hipStream_t)stream>>>(n, problems, tile_prefix, workspace,
-                                                                                    sync);
-  return (int)hipGetLastError();
 }
 
 extern "C" int msr3d_wgrad_split_mixed(int n, const msr3d_wgrad_problem_t *problems, const int *tile_prefix,

@@ -39,16 +39,6 @@ def set_train_mma(name):
     return prev
 
 
-def set_attn_fwd_form(split):
-    """The attention forward block as two workgroups per (scene, head) (True: the library's default, best when the step has
-    the chip to itself) or one (False: best in the pipelined schedule, where the next batch's encoder runs beside the
-    trainable part); applies to every loaded library; takes effect at the next launch (a captured graph keeps its form)."""
-    form = 1 if split else 0
-    for lib in (_lib.load(), _lib._lib_bf16):
-        if lib is not None:
-            lib.msr3d_attn_fwd_form(form)
-
-
 def _klib():
     """The library whose block / weight-gradient kernels run."""
     return _lib.load_bf16() if _TRAIN_MMA[0] == "bf16" else _lib.load()
@@ -141,15 +131,10 @@ class WgradTable:
         self._dirty = True
         self._pin = None
         self._ev = None
-        # MSR3D_WGRAD_HALVES=1: every tile's reduction as two units with a ticket hand-over (msr3d_wgrad_split_halves).
-        # Built to remove the second, 41 %-full round of the 360 one-per-CU tiles; measured SLOWER in the step (1.306 vs
-        # 1.290 ms: two pipeline fills, the parked 64 KB image and the release / acquire fences per tile cost more than the
-        # tail they remove), so the default stays one workgroup per tile.  Kept, tested, opt-in.
-        self.halves = os.environ.get("MSR3D_WGRAD_HALVES", "0") == "1"
         # Round 5 (default; MSR3D_WGRAD_MIXED=0 turns it off): only the tiles of the launch's PARTIAL round are cut in two
         # (msr3d_wgrad_split_mixed) -- ~330 real tiles on 256 CUs are one full round and one that is 29 % full; with those
         # 74 tiles as 148 half-reductions the second round lasts half a tile time.
-        self.mixed = os.environ.get("MSR3D_WGRAD_MIXED", "1") != "0" and not self.halves
+        self.mixed = os.environ.get("MSR3D_WGRAD_MIXED", "1") != "0"
         self._ws = self._sync = None
         self._real = []                       # real (non-padding) tiles of each problem
         # Round 6 (default; MSR3D_WGRAD_STREAM=0 turns it off): the tiles as one sequence of slab pairs dealt evenly to a
@@ -158,8 +143,9 @@ class WgradTable:
         # per workgroup each pay a prologue and a write-back, which is what the even deal saves); IN THE STEP it is 8-12 us
         # faster (0.851 against 0.862 ms, three interleaved pairs: profiles/r06_v2_ab.txt).  Bit-reproducible.  Needs the
         # pipe tile kernel (msr3d_wgrad_form 1).
-        self.stream = os.environ.get("MSR3D_WGRAD_STREAM", "1") != "0" and not self.halves
-        self._stream_key = None
+        self.stream = os.environ.get("MSR3D_WGRAD_STREAM", "1") != "0"
+        self._stream_plans = {}               # key -> plan (or None), never dropped: see _plan_stream
+        self._stream_key = None               # the entry of the last launch
         self._stream_plan = None
 
     def add(self, dy, ldy, n_out, x, ldx, k_in, M, dW, ldw, db):
@@ -204,9 +190,9 @@ class WgradTable:
                 local = ((lb - p.xcd_rot) & 7) * (nb >> 3) + (lb >> 3)     # (the kernel's XCD-aware order)
                 real.append(local < r and p.M > 0)
         # Measured (tools/bench_wgrad.py, the step's 326 real tiles of 360 workgroups on 256 CUs): whole tiles only 115 us,
-        # every tile halved 129 us, the last 96-136 workgroups halved 110 us -- a unit costs ~27 us besides its slabs
-        # (its life is set by the loader waves: 16 waves of splitting VALU + MFMA issue on one CU), so cutting helps only
-        # the tail.  W: the real tiles left whole number one per CU less a sixteenth (the halves then start on CUs that
+        # every tile halved (a launch form since removed) 129 us, the last 96-136 workgroups halved 110 us -- a unit costs
+        # ~27 us besides its slabs (its life is set by the loader waves: 16 waves of splitting VALU + MFMA issue on one
+        # CU), so cutting helps only the tail.  W: the real tiles left whole number one per CU less a sixteenth (the halves then start on CUs that
         # are already free); nothing is cut when the tiles fit one round or the rest would not fit a second.
         total_real, whole = sum(real), self.prefix[-1]
         target = cus - cus // 16
@@ -219,14 +205,22 @@ class WgradTable:
         self._whole_key, self._whole = key, whole
         return whole
 
+    def _plan_key(self, n_jobs):
+        return (tuple((p.M, p.n_out, p.k_in) for p in self.probs), n_jobs)
+
     PIECE_CHARGE = 2          # what a piece costs besides its slab pairs (prologue + write-back), in slab pairs
 
     def _plan_stream(self, n_jobs, cus=None, upload=True):
         """-> (pieces tensor, wg_first tensor, n_pieces, n_wgs, n_slots) for msr3d_wgrad_stream, or None when the problem set
         is too small to deal (fewer slab pairs than one tile's worth per workgroup: the plain launch is already one round).
-        Rebuilt when a problem's token count changes (llm_proj's is 0 in a step without an upstream gradient)."""
-        key = (tuple((p.M, p.n_out, p.k_in) for p in self.probs), n_jobs)
-        if self._stream_key == key:
+        One plan per key -- the problems' (token count, n_out, k_in) and n_jobs; llm_proj's token count is 0 in a step without
+        an upstream gradient -- built at the key's first launch and kept for the table's lifetime: a captured graph holds the
+        raw addresses of a plan's device tensors, so like `_table` and `_ws` they must never move or be freed while another
+        key is in use.  An entry is a few KB, and their number is bounded by the distinct token-count tuples a model sees.
+        `_stream_key` / `_stream_plan` name the entry of the last call."""
+        key = self._plan_key(n_jobs)
+        if upload and key in self._stream_plans:
+            self._stream_key, self._stream_plan = key, self._stream_plans[key]
             return self._stream_plan
         C = self.PIECE_CHARGE
         tiles = []                           # (problem, ntile, ktile, slab pairs): consecutive k tiles share a dy block
@@ -305,7 +299,9 @@ class WgradTable:
                 plan = (_device_bytes(arr, self.device), torch.tensor(first_idx, dtype=torch.int32).to(self.device),
                         len(flat), n_wgs, slots, max(load), min(load),
                         torch.tensor(slot_piece or [0], dtype=torch.int32).to(self.device))
-        self._stream_key, self._stream_plan = key, plan
+        if upload:
+            self._stream_plans[key] = plan
+            self._stream_key, self._stream_plan = key, plan
         return plan
 
     def set_ptr(self, idx, field, ptr):
@@ -339,24 +335,11 @@ class WgradTable:
                 self._ev = torch.cuda.Event()
                 self._ev.record()
             self._dirty = False
-        if self.halves:
-            # every tile's token reduction as two units (2 x tiles workgroups): ~1.4 tiles per CU spread evenly
-            # instead of two rounds with a 41 %-full second one; partial hand-over through `_ws`, tickets in `_sync`
-            if self._ws is None:
-                self._ws = torch.empty(self.prefix[-1] * HALF_SLOT_FLOATS, dtype=torch.float32, device=self.device)
-                self._sync = torch.zeros(2 * self.prefix[-1], dtype=torch.int32, device=self.device)
-            rc = _klib().msr3d_wgrad_split_halves(len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                                      self.prefix[-1], _vp(self._ws.data_ptr()), self._ws.numel(),
-                                                      _vp(self._sync.data_ptr()), stream)
-            _lib.check(rc, "msr3d_wgrad_split_halves")
-            if colsum is not None:
-                _lib.check(_lib.load().msr3d_colsum_partials(colsum[0], _vp(colsum[1].data_ptr()), stream), "msr3d_colsum_partials")
-            return
         if self.stream and _klib().msr3d_wgrad_form(-1) == 1:
-            if torch.cuda.is_current_stream_capturing() and self._stream_key != (
-                    tuple((p.M, p.n_out, p.k_in) for p in self.probs), colsum[0] if colsum is not None else 0):
+            n_jobs = colsum[0] if colsum is not None else 0
+            if torch.cuda.is_current_stream_capturing() and self._plan_key(n_jobs) not in self._stream_plans:
                 raise RuntimeError("WgradTable: the stream plan must exist before a graph capture (launch once eagerly)")
-            plan = self._plan_stream(colsum[0] if colsum is not None else 0)
+            plan = self._plan_stream(n_jobs)
             if plan is not None:
                 pieces, first, n_pieces, n_wgs, slots = plan[:5]
                 if slots and (self._ws is None or self._ws.numel() < slots * HALF_SLOT_FLOATS):

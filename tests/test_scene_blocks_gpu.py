@@ -65,10 +65,8 @@ def test_split_pack_matches_the_exact_split_bit_for_bit():
     assert np.max(np.abs(back - w) / np.abs(w)) < 2.0 ** -23
 
 
-@pytest.mark.parametrize("halves", [False, True])
 @pytest.mark.parametrize("M,n_out,k_in", [(960, 256, 2048), (976, 816, 256), (150, 256, 63), (37, 256, 3), (960, 4096, 256)])
-def test_wgrad_split_vs_float64(M, n_out, k_in, halves):
-    """halves: msr3d_wgrad_split_halves -- two units per tile, ticket hand-over of the first starter's partial."""
+def test_wgrad_split_vs_float64(M, n_out, k_in):
     from msr3d_amd import _lib
     from msr3d_amd.scene_blocks import WgradTable
     torch.manual_seed(M + n_out)
@@ -79,7 +77,6 @@ def test_wgrad_split_vs_float64(M, n_out, k_in, halves):
     db0 = torch.randn(n_out, device="cuda")
     dW, db = dW0.clone(), db0.clone()
     t = WgradTable(dy.device)
-    t.halves = halves
     t.add(dy.data_ptr(), n_out, n_out, x.data_ptr(), xw.stride(0), k_in, M, dW.data_ptr(), k_in, db.data_ptr())
     t.launch(_lib.current_stream_ptr(dy.device))
     torch.cuda.synchronize()
@@ -169,6 +166,53 @@ def test_wgrad_stream_launch_is_bit_reproducible():
         outs.append(res)
     for (a, ab), (b, bb) in zip(*outs):
         assert torch.equal(a, b) and torch.equal(ab, bb)
+
+
+def test_wgrad_stream_plans_keep_their_device_tensors_across_token_count_changes():
+    """A problem's token count toggling between M and 0 (fused_model does it to llm_proj's in a step without an upstream
+    gradient) alternates between two stream plans.  A captured graph holds the raw addresses of a plan's device tensors, so
+    a replay is safe only if every plan ever launched keeps its tensors, where they are, with their contents, whatever key is
+    launched afterwards: the plans of key A at the third launch ARE those of the first, key B's stay alive beside them, and
+    the first and third launches give the same bits."""
+    from msr3d_amd import _lib
+    from msr3d_amd.scene_blocks import WgradTable
+    dev = torch.device("cuda")
+    st = _lib.current_stream_ptr(dev)
+    torch.manual_seed(23)
+    ops = []
+    for M, n_out, k_in in [(256, 256, 2048), (256, 2048, 256), (256, 256, 256)]:
+        ops.append((torch.randn(M, n_out, device=dev), torch.randn(M, k_in, device=dev), torch.randn(n_out, k_in, device=dev),
+                    torch.randn(n_out, device=dev)))
+    t = WgradTable(dev)
+    t.stream = True
+    for dy, x, dW0, db0 in ops:
+        t.add(dy.data_ptr(), dy.shape[1], dy.shape[1], x.data_ptr(), x.shape[1], x.shape[1], dy.shape[0], 0, x.shape[1], 0)
+
+    def launch(m_third):
+        res = [(dW0.clone(), db0.clone()) for _, _, dW0, db0 in ops]          # fresh clones of the same initial values
+        for i, (dW, db) in enumerate(res):
+            t.set_ptr(i, "dW", dW.data_ptr())
+            t.set_ptr(i, "db", db.data_ptr())
+        t.set_ptr(2, "M", m_third)
+        t.launch(st)
+        torch.cuda.synchronize()
+        plan = t._stream_plan
+        assert plan is not None and plan[4] > 0                               # (a real deal, with cut tiles, for both keys)
+        tensors = [plan[0], plan[1], plan[7]]                                 # pieces, wg_first, slot_piece
+        return res, tensors, t._stream_key, [(x.data_ptr(), x.cpu().clone()) for x in tensors]
+
+    res_a, tens_a, key_a, snap_a = launch(256)
+    _, _, key_b, snap_b = launch(0)                     # (key B's tensors are held by the table alone from here on)
+    assert key_b != key_a and not {p for p, _ in snap_a} & {p for p, _ in snap_b}
+    res_c, tens_c, key_c, _ = launch(256)
+    assert key_c == key_a
+    for xa, xc, (pa, ha) in zip(tens_a, tens_c, snap_a):
+        assert xc is xa and xc.data_ptr() == pa and torch.equal(xc.cpu(), ha)
+    plan_b = t._stream_plans[key_b]
+    for xb, (pb, hb) in zip([plan_b[0], plan_b[1], plan_b[7]], snap_b):
+        assert xb.data_ptr() == pb and torch.equal(xb.cpu(), hb)
+    for (a, ab), (c, cb) in zip(res_a, res_c):
+        assert torch.equal(a, c) and torch.equal(ab, cb)
 
 
 def _rel(a, b):

@@ -1,5 +1,5 @@
 """msr3d_wgrad_split on the bench step's problem set (synthetic operands), the launch forms side by side:
-whole tiles / mixed (tiles of the partial round as two half-reductions) / every tile halved.
+whole tiles / mixed (tiles of the partial round as two half-reductions) / the stream deal.
     python tools/bench_wgrad.py"""
 import os
 import sys
@@ -14,9 +14,8 @@ M, D, FF, W, E, KE = 960, 256, 2048, 816, 4096, 768
 dev = torch.device("cuda")
 
 
-def build(mixed, halves=False):
+def build(mixed):
     os.environ["MSR3D_WGRAD_MIXED"] = "1" if mixed else "0"
-    os.environ["MSR3D_WGRAD_HALVES"] = "1" if halves else "0"
     t = WgradTable(dev)
     keep = []
 
@@ -36,7 +35,7 @@ st = _lib.current_stream_ptr(dev)
 for form in (0, 1):
   _lib.load().msr3d_wgrad_form(form)
   print("tile kernel:", "pipe (8 waves, round 6)" if form else "loader + multiplier waves (rounds 4-5)")
-  for name, kw in (("whole tiles", dict(mixed=False)), ("mixed", dict(mixed=True)), ("all halved", dict(mixed=False, halves=True)),
+  for name, kw in (("whole tiles", dict(mixed=False)), ("mixed", dict(mixed=True)),
                    ("stream", dict(mixed=True, stream=True))):
       if kw.get("stream") and not form:
           continue

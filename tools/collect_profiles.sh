@@ -44,13 +44,7 @@ v env MSR3D_WGRAD_PIPE=0 python bench.py --full --no-cpu-baseline
 v env MSR3D_WGRAD_STREAM=1 python bench.py --full --no-cpu-baseline
 v env MSR3D_PACK_FORK=1 python bench.py --full --no-cpu-baseline
 v env MSR3D_SA3_TILE=2 python bench.py --full --no-cpu-baseline
-v env MSR3D_WGRAD_HALVES=1 python bench.py --full --no-cpu-baseline
-v env MSR3D_ATTN_FWD_WAVES=4 MSR3D_ATTN_FWD_SPLIT=0 python bench.py --full --no-cpu-baseline
-v env MSR3D_ATTN_FWD_SPLIT=0 python bench.py --full --no-cpu-baseline
-v env MSR3D_ATTN_BWD=2 python bench.py --full --no-cpu-baseline
-v env MSR3D_ATTN_BWD=0 python bench.py --full --no-cpu-baseline
 v env MSR3D_FC_SPLIT=0 python bench.py --full --no-cpu-baseline
-v env MSR3D_FFN_WAVES=4 python bench.py --full --no-cpu-baseline
 v env MSR3D_SA_PLAN12=0 python bench.py --full --no-cpu-baseline
 v env MSR3D_SA_PLAN_IN_SAMPLING=0 python bench.py --full --no-cpu-baseline
 v env MSR3D_SA3_TILES=0 python bench.py --full --no-cpu-baseline

@@ -43,7 +43,7 @@ def launch_block(stream, **kw):
     name = KIND[s.kind]
     slices = 8 if name.startswith("attn") else int(s.ff) // 128 if name.startswith("ffn") else \
         int(s.N) // 256 if name == "linear" else int(s.lda0) // 256
-    if name == "attn_fwd" and os.environ.get("MSR3D_ATTN_FWD_SPLIT", "1") != "0":
+    if name == "attn_fwd":
         slices = 16                      # two workgroups per (scene, head)
     nblk = int(s.B) * slices
     wpb = max(len(st) // max(nblk, 1), 1)
