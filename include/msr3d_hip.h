@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 32
+#define MSR3D_ABI_VERSION 33
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -957,6 +957,16 @@ int msr3d_bf16_gemm_lowrank(int M, int N, int K, int R, const void *P, int ldp, 
 int msr3d_bf16_gemm_lowrank_acc(int M, int N, int K, int R, const void *P, int ldp, const void *Q, int ldq,
                                 const void *P2, int ldp2, const void *Q2, int ldq2, void *C, int ldc, float scale,
                                 msr3d_stream_t stream);
+
+/* Which kernel the three entries above launch for a shape (host only, no launch; the entries call these same functions):
+ * msr3d_bf16_gemm_path: 0 = bf16_gemm_kernel<128>, 1 = bf16_gemm_kernel<192>, 2 = bf16_gemm_glds_kernel<192>, 8 / 9 / 10 =
+ *   the wide-tile kernel at tile height 128 / 144 / 160; batch = outer * inner (1 for msr3d_bf16_gemm_lowrank); honours
+ *   MSR3D_BF16_GEMM (wide | glds | reg, read once per process) as the launch does.
+ * msr3d_bf16_gemm_acc_tile, msr3d_fp8_gemm_tile: the wide tile's height (128, 144 or 160) msr3d_bf16_gemm_lowrank_acc and
+ *   msr3d_fp8_gemm_lowrank(_acc) take.  MSR3D_EINVAL for an empty shape. */
+int msr3d_bf16_gemm_path(int M, int N, int R, int batch, int ldp, int ldq, int ldp2, int ldq2);
+int msr3d_bf16_gemm_acc_tile(int M, int N);
+int msr3d_fp8_gemm_tile(int M, int N);
 
 /* LoRA weight gradients' token reduction: out (R, C) f32 (+)= scale * sum_m P[m][r] Q[m][c]
  * (transpose_out: out is (C, R)); P (M, R) and Q (M, C) bf16; R in {16, 32}; `out` holds the value to

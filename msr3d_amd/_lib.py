@@ -138,6 +138,9 @@ _SIGNATURES = {
     "msr3d_bf16_gemm_batched": [_c_int] * 5 + [_ptr, _c_int, ctypes.c_longlong, ctypes.c_longlong, _ptr, _c_int,
                                 ctypes.c_longlong, ctypes.c_longlong, _ptr, _c_int, ctypes.c_longlong,
                                 ctypes.c_longlong, _c_int, _c_float, _ptr],
+    "msr3d_bf16_gemm_path": [_c_int] * 8,
+    "msr3d_bf16_gemm_acc_tile": [_c_int, _c_int],
+    "msr3d_fp8_gemm_tile": [_c_int, _c_int],
     "msr3d_rmsnorm_fwd": [_c_int, _c_int, _ptr, _ptr, _ptr, _c_float, _ptr, _ptr, _ptr, _ptr],
     "msr3d_rmsnorm_bwd": [_c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_rope_inplace": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr],
@@ -273,7 +276,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 32       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 33       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():

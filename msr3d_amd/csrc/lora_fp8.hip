@@ -325,17 +325,13 @@ static int fp8_gemm(int M, int N, int K, const void *Pq, int ldp, const float *s
   a.Q2 = (const unsigned short *)Q2; a.ldq2 = ldq2;
   a.C = (unsigned short *)C; a.ldc = ldc;
   a.accumulate = accumulate;
-  // tile height = the one with the least (rounds of 256 CUs) x height, as the bf16 kernel picks it
-  const int tn = (N + WBN - 1) / WBN;
-  long long best = -1;
-  int bm = 0;
-  for (int h : {160, 144, 128}) {
-    const long long tiles = (long long)((M + h - 1) / h) * tn, cost = ((tiles + 255) / 256) * h;
-    if (best < 0 || cost < best) { best = cost; bm = h; }
-  }
+  const int bm = msr3d_fp8_gemm_tile(M, N);
   hipStream_t st = (hipStream_t)stream;
   return bm == 160 ? launch<10>(a, st) : bm == 144 ? launch<9>(a, st) : launch<8>(a, st);
 }
+
+// tile height = the one with the least (rounds of 256 CUs) x height: the bf16 wide kernel's rule, stated there
+int msr3d_fp8_gemm_tile(int M, int N) { return msr3d_bf16_gemm_acc_tile(M, N); }
 
 int msr3d_fp8_gemm_lowrank(int M, int N, int K, const void *Pq, int ldp, const float *sp, const void *Qq, int ldq,
                            const float *sq, const void *P2, int ldp2, const void *Q2, int ldq2, void *C, int ldc,

@@ -1006,36 +1006,53 @@ int launch_gemm_wide(const GemmArgs &a, int batch, hipStream_t st) {
 
 std::atomic<int> g_gemm_path{-1};                // -1: read MSR3D_BF16_GEMM (wide | glds | reg) on first use
 
-int gemm_dispatch(GemmArgs &a, int batch, hipStream_t st) {
+// wide tiles: tile height = the one with the least (rounds of 256 CUs) x height
+int wide_tile_height(int M, int N, int batch) {
+  const int tn = (N + WBN - 1) / WBN;
+  long long best = -1;
+  int bm = 0;
+  for (int h : {160, 144, 128}) {
+    const long long tiles = (long long)((M + h - 1) / h) * tn * batch, cost = (tiles + 255) / 256 * h;
+    if (best < 0 || cost < best) best = cost, bm = h;
+  }
+  return bm;
+}
+
+// the kernel a product takes, from its shape alone: 0 = bf16_gemm_kernel<128>, 1 = bf16_gemm_kernel<192>,
+// 2 = bf16_gemm_glds_kernel<192>, 8 / 9 / 10 = bf16_gemm_wide_kernel<MTB> (msr3d_bf16_gemm_path reports it)
+int gemm_path(int M, int N, int R, int batch, int ldp, int ldq, int ldp2, int ldq2) {
   int path = g_gemm_path.load(std::memory_order_relaxed);
   if (path < 0) {
     const char *e = getenv("MSR3D_BF16_GEMM");
     path = (e && e[0] == 'r') ? 0 : (e && e[0] == 'g') ? 1 : 2;
     g_gemm_path.store(path, std::memory_order_relaxed);
   }
-  // wide tiles: big products whose offsets fit the kernel's 32-bit element offsets; tile height = the one with the
-  // least (rounds of 256 CUs) x height
-  if (path == 2 && a.M >= 128 && a.N >= 256 && (a.R % BK) == 0 &&
-      (long long)a.M * a.ldp < (1ll << 31) && (long long)a.N * a.ldq < (1ll << 31) &&
-      (a.R == 0 || ((long long)a.M * a.ldp2 < (1ll << 31) && (long long)a.N * a.ldq2 < (1ll << 31)))) {
-    const int tn = (a.N + WBN - 1) / WBN;
-    long long best = -1;
-    int bm = 0;
-    for (int h : {160, 144, 128}) {
-      const long long tiles = (long long)((a.M + h - 1) / h) * tn * batch, cost = (tiles + 255) / 256 * h;
-      if (best < 0 || cost < best) best = cost, bm = h;
-    }
+  // wide tiles: big products whose offsets fit the kernel's 32-bit element offsets
+  if (path == 2 && M >= 128 && N >= 256 && (R % BK) == 0 &&
+      (long long)M * ldp < (1ll << 31) && (long long)N * ldq < (1ll << 31) &&
+      (R == 0 || ((long long)M * ldp2 < (1ll << 31) && (long long)N * ldq2 < (1ll << 31)))) {
+    const int bm = wide_tile_height(M, N, batch);
     // (fewer tiles than half the chip: the 128-wide tiles of the 4-wave kernels spread the product further)
-    if ((long long)((a.M + bm - 1) / bm) * tn * batch >= 128)
-      return bm == 160 ? launch_gemm_wide<10>(a, batch, st) : bm == 144 ? launch_gemm_wide<9>(a, batch, st)
-                                                                        : launch_gemm_wide<8>(a, batch, st);
+    if ((long long)((M + bm - 1) / bm) * ((N + WBN - 1) / WBN) * batch >= 128) return bm / 16;
   }
   // LDS-DMA path: rows >= 16 bytes-aligned sources (checked by the callers) and R a multiple of 64 (a stage
   // reads 64 columns of the low-rank pair)
-  if (path >= 1 && a.M >= 192 && (a.R % BK) == 0) return launch_gemm_glds<192>(a, batch, st);
+  if (path >= 1 && M >= 192 && (R % BK) == 0) return 2;
   // tile height: the one that wastes fewer padded rows; 192 on a tie at >= 192 rows (fewer LDS reads per MFMA)
-  const long long w128 = (long long)((a.M + 127) / 128) * 128, w192 = (long long)((a.M + 191) / 192) * 192;
-  return (a.M >= 192 && w192 <= w128) ? launch_gemm<192>(a, batch, st) : launch_gemm<128>(a, batch, st);
+  const long long w128 = (long long)((M + 127) / 128) * 128, w192 = (long long)((M + 191) / 192) * 192;
+  return (M >= 192 && w192 <= w128) ? 1 : 0;
+}
+
+int launch_wide(int mtb, const GemmArgs &a, int batch, hipStream_t st) {
+  return mtb == 10 ? launch_gemm_wide<10>(a, batch, st) : mtb == 9 ? launch_gemm_wide<9>(a, batch, st)
+                                                                   : launch_gemm_wide<8>(a, batch, st);
+}
+
+int gemm_dispatch(GemmArgs &a, int batch, hipStream_t st) {
+  const int path = gemm_path(a.M, a.N, a.R, batch, a.ldp, a.ldq, a.ldp2, a.ldq2);
+  if (path >= 8) return launch_wide(path, a, batch, st);
+  return path == 2 ? launch_gemm_glds<192>(a, batch, st) : path == 1 ? launch_gemm<192>(a, batch, st)
+                                                                     : launch_gemm<128>(a, batch, st);
 }
 
 }  // namespace
@@ -1085,15 +1102,17 @@ int msr3d_bf16_gemm_lowrank_acc(int M, int N, int K, int R, const void *P, int l
   a.accumulate = 1;
   a.inner = 1;
   a.spo = a.spi = a.sqo = a.sqi = a.sco = a.sci = 0;
-  const int tn = (N + WBN - 1) / WBN;
-  long long best = -1;
-  int bm = 0;
-  for (int h : {160, 144, 128}) {
-    const long long tiles = (long long)((M + h - 1) / h) * tn, cost = (tiles + 255) / 256 * h;
-    if (best < 0 || cost < best) best = cost, bm = h;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  return bm == 160 ? launch_gemm_wide<10>(a, 1, st) : bm == 144 ? launch_gemm_wide<9>(a, 1, st) : launch_gemm_wide<8>(a, 1, st);
+  return launch_wide(msr3d_bf16_gemm_acc_tile(M, N) / 16, a, 1, (hipStream_t)stream);
+}
+
+int msr3d_bf16_gemm_path(int M, int N, int R, int batch, int ldp, int ldq, int ldp2, int ldq2) {
+  if (M <= 0 || N <= 0 || R < 0 || batch <= 0) return MSR3D_EINVAL;
+  return gemm_path(M, N, R, batch, ldp, ldq, ldp2, ldq2);
+}
+
+int msr3d_bf16_gemm_acc_tile(int M, int N) {
+  if (M <= 0 || N <= 0) return MSR3D_EINVAL;
+  return wide_tile_height(M, N, 1);
 }
 
 int msr3d_bf16_gemm_batched(int outer, int inner, int M, int N, int K, const void *P, int ldp, long long p_outer,

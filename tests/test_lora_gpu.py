@@ -18,7 +18,9 @@ def bf(t):
 
 
 @pytest.mark.parametrize("M,K,N,r", [(2304, 4096, 4096, 16), (300, 4096, 11008, 16), (129, 11008, 4096, 16),
-                                     (64, 256, 192, 32), (4000, 512, 256, 16)])      # (>= 3584 rows: 16-row skinny tiles)
+                                     (64, 256, 192, 32), (4000, 512, 256, 16),       # (>= 3584 rows: 16-row skinny tiles)
+                                     # 4 sequences x 640 tokens: the wide-tile kernel at tile height 160, forward and dx
+                                     (2560, 4096, 4096, 16), (2560, 4096, 11008, 16)])
 def test_lora_linear_matches_the_float64_formulation(M, K, N, r):
     from msr3d_amd.llm import LoRALinear
     torch.manual_seed(M + N)
