@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 33
+#define MSR3D_ABI_VERSION 34
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1107,6 +1107,11 @@ int msr3d_lora_shadows(int njobs, const msr3d_lora_shadow_job_t *jobs_device, ms
  *   workgroup splitting K; v_mfma_f32_16x16x32_bf16 with the activations as the 16-row side.  q / k / v are one call
  *   (njobs = 3).  swiglu != 0: njobs == 2 (gate, up; N_0 == N_1) and C_0 = bf16(silu(bf16 gate)) * bf16 up, the
  *   roundings of msr3d_swiglu_fwd on bf16 projections; C_1 is not written.  `jobs` is HOST memory, read during the call.
+ * msr3d_bf16_skinny_lowrank_wide: the same arguments and contract for M <= MSR3D_SKINNY_WIDE_MAX_M (ABI v34).  Up to
+ *   MSR3D_SKINNY_MAX_M rows it launches what msr3d_bf16_skinny_lowrank launches (the same bits); 33 .. 64 rows are three
+ *   or four 16-row activation tiles per workgroup, with 32 rows of W per workgroup wherever that leaves >= 256
+ *   workgroups.  A row of C is computed from that row of P and P2 alone; rows >= M are read clamped and never stored.
+ *   msr3d_bf16_skinny_lowrank itself still refuses M > MSR3D_SKINNY_MAX_M.
  * msr3d_rope_positions: x0 and (optional) x1 (B, T, H, D) bf16 rotated in place by pos (B, T) int32 (clamped to
  *   0 .. table_rows - 1); cos / sin (table_rows, D) f32 as msr3d_rope_inplace reads; D % 16 == 0.  pos == arange(T): the
  *   bits of msr3d_rope_inplace2.
@@ -1129,6 +1134,7 @@ int msr3d_lora_shadows(int njobs, const msr3d_lora_shadow_job_t *jobs_device, ms
  *   V <= MSR3D_DECODE_SELECT_MAX_V (the row lives in LDS as fp32), k <= MSR3D_DECODE_SELECT_MAX_K.  out_val, out_tok (N, k).
  * ------------------------------------------------------------------------- */
 #define MSR3D_SKINNY_MAX_M 32
+#define MSR3D_SKINNY_WIDE_MAX_M 64
 #define MSR3D_ATTN_DECODE_MAX_SPLITS 8
 #define MSR3D_DECODE_SELECT_MAX_V 40000
 #define MSR3D_DECODE_SELECT_MAX_K 64
@@ -1140,6 +1146,8 @@ typedef struct {
 } msr3d_skinny_job_t;
 int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
                               const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
+int msr3d_bf16_skinny_lowrank_wide(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                                   const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
 int msr3d_rope_positions(int B, int T, int H, int D, void *x0, void *x1, const int *pos, const float *cos_td,
                          const float *sin_td, int table_rows, msr3d_stream_t stream);
 int msr3d_rope_kv_append(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,

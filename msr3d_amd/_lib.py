@@ -161,6 +161,8 @@ _SIGNATURES = {
     "msr3d_lora_shadows": [_c_int, _ptr, _ptr],
     "msr3d_bf16_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, ctypes.POINTER(SkinnyJob),
                                   _c_int, _ptr],
+    "msr3d_bf16_skinny_lowrank_wide": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int,
+                                       ctypes.POINTER(SkinnyJob), _c_int, _ptr],
     "msr3d_rope_positions": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
     "msr3d_rope_kv_append": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr,
                              _ptr, _ptr],
@@ -276,7 +278,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 33       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 34       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():

@@ -1,7 +1,9 @@
 // llm_decode.hip -- the kernels of one KV-cached decoding step of the LoRA-Llama stack (msr3d_amd/llm/generate.py):
-// what transformers' `generate` runs per new token, for N <= 32 live rows (batch x beams).
+// what transformers' `generate` runs per new token, for N <= 64 live rows (batch x beams); `search` walks a larger batch
+// in groups of whole prompts.
 //
 //     msr3d_bf16_skinny_lowrank   C (M <= 32, N) = P W^T + P2 B2^T      every projection and the head: a weight stream
+//     msr3d_bf16_skinny_lowrank_wide   the same for M <= 64: three and four activation tiles a workgroup
 //     msr3d_rope_kv_append        rotate q, k by the row's own position, write k, v into cache slot len[n]
 //     msr3d_rope_positions        the prefill twin: (B, T, H, D) rotated by pos (B, T)
 //     msr3d_attn_decode           one query row per (row, head) against the row's cache: a stream over K and V
@@ -63,6 +65,12 @@ __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
 // matrix pipe works on this one, and add their partial sums through LDS in wave order.  The activations (M rows, a few
 // hundred KB at most) are read from L2 by every workgroup -- 32 x 11008 bf16 do not fit the 160 KB of LDS, and staging
 // K in slices would put a barrier into the weight stream.
+// MT = 3, 4 (33 .. 64 rows, the wide entry): a[MT][4] and its prefetch copy are 32 MT registers; MT = 4, TN = 2 compiles to
+// 222 VGPRs + 32 AGPRs, no scratch, two waves a SIMD, 32 KB of LDS.  Row m of an accumulator tile comes from row m of the
+// activation operand alone, so a row of C never sees another row of P (NaN included), whatever MT.
+
+// the wide entry takes two tiles of W a workgroup only where that still gives every CU of the part a workgroup
+constexpr long long kSkinnyWideMinWg = 256;
 struct SkinnyJobs {
   const u16 *W[3];
   const u16 *B2[3];
@@ -517,28 +525,40 @@ __global__ __launch_bounds__(256) void decode_select_kernel(int V, const u16 *__
 
 extern "C" {
 
-int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
-                              const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
-  if (M < 0 || M > MSR3D_SKINNY_MAX_M || K <= 0 || (K % 128) || R < 0 || (R % 32) || njobs < 1 || njobs > 3 || !jobs)
+// Both skinny entries: `max_m` is the entry's row limit.  M <= 32 takes the one- and two-tile kernels under the tile rule
+// they always had (the bits of msr3d_bf16_skinny_lowrank do not depend on which entry was called); 33 .. 64 rows take the
+// three- and four-tile instantiations under the wide rule below.
+static int skinny_launch(int max_m, int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                         const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
+  if (M < 0 || M > max_m || K <= 0 || (K % 128) || R < 0 || (R % 32) || njobs < 1 || njobs > 3 || !jobs)
     return MSR3D_EINVAL;
   if (!P || ldp < K || (ldp % 8) || !al16(P)) return MSR3D_EINVAL;
   if (R > 0 && (!P2 || ldp2 < R || (ldp2 % 8) || !al16(P2))) return MSR3D_EINVAL;
   if (swiglu && (njobs != 2 || jobs[0].N != jobs[1].N || !jobs[0].C)) return MSR3D_EINVAL;
-  // two 16-row tiles of W per workgroup where that still leaves every CU several workgroups (the activations are read
-  // once per workgroup); gate | up with the SwiGLU epilogue is always the pair
   long long rows = 0;
+  bool pairs = true;                                  // every job's N a multiple of 32: two tiles a workgroup possible
   for (int j = 0; j < njobs; ++j) {
     const msr3d_skinny_job_t &jb = jobs[j];
     if (jb.N <= 0 || (jb.N % 16) || !jb.W || jb.ldw < K || (jb.ldw % 8) || !al16(jb.W)) return MSR3D_EINVAL;
     if (R > 0 && jb.B2 && (jb.ldb2 < R || (jb.ldb2 % 8) || !al16(jb.B2))) return MSR3D_EINVAL;
     if (!(swiglu && j == 1) && (!jb.C || jb.ldc < jb.N)) return MSR3D_EINVAL;
     rows += jb.N;
+    if (jb.N % 32) pairs = false;
   }
   if (M == 0) return 0;
-  int tn = (swiglu || rows >= 16384) ? 2 : 1;
-  if (!swiglu && tn == 2)
-    for (int j = 0; j < njobs; ++j)
-      if (jobs[j].N % 32) tn = 1;
+  const int mt = (M + 15) / 16;
+  int tn;
+  if (mt <= 2) {
+    // two 16-row tiles of W per workgroup where that still leaves every CU several workgroups (the activations are read
+    // once per workgroup); gate | up with the SwiGLU epilogue is always the pair
+    tn = (swiglu || (rows >= 16384 && pairs)) ? 2 : 1;
+  } else {
+    // 33 .. 64 rows: a workgroup reads M K activations out of L2 for 16 tn rows of W out of HBM, M / (16 tn) bytes for
+    // one, so the pair halves the L2 traffic -- but only pays where it still gives every CU a workgroup.  Measured at
+    // 64 rows: the head 95 us against 147 and q | k | v (384 workgroups as pairs) 51 against 61 with the
+    // pair; o and down (N = 4096: 128 workgroups as pairs) 28 against 23 and 69 against 55, so those keep one tile.
+    tn = (swiglu || (pairs && rows / 32 >= kSkinnyWideMinWg)) ? 2 : 1;
+  }
   SkinnyJobs sj{};
   sj.njobs = njobs;
   long long grid = 0;
@@ -551,13 +571,30 @@ int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const
   if (swiglu) grid = sj.tiles[0];
   hipStream_t st = (hipStream_t)stream;
   const u16 *p = (const u16 *)P, *p2 = (const u16 *)P2;
-  const int mt = M <= 16 ? 1 : 2;
 #define MSR3D_SK(MT, TN, SW) skinny_kernel<MT, TN, SW><<<(unsigned)grid, 256, 0, st>>>(M, K, R, p, ldp, p2, ldp2, sj)
-  if (swiglu) { if (mt == 1) MSR3D_SK(1, 2, true); else MSR3D_SK(2, 2, true); }
-  else if (tn == 2) { if (mt == 1) MSR3D_SK(1, 2, false); else MSR3D_SK(2, 2, false); }
-  else { if (mt == 1) MSR3D_SK(1, 1, false); else MSR3D_SK(2, 1, false); }
+#define MSR3D_SK_MT(TN, SW)                                                                                            \
+  switch (mt) {                                                                                                        \
+    case 1: MSR3D_SK(1, TN, SW); break;                                                                                \
+    case 2: MSR3D_SK(2, TN, SW); break;                                                                                \
+    case 3: MSR3D_SK(3, TN, SW); break;                                                                                \
+    default: MSR3D_SK(4, TN, SW); break;                                                                               \
+  }
+  if (swiglu) { MSR3D_SK_MT(2, true) }
+  else if (tn == 2) { MSR3D_SK_MT(2, false) }
+  else { MSR3D_SK_MT(1, false) }
+#undef MSR3D_SK_MT
 #undef MSR3D_SK
   return (int)hipGetLastError();
+}
+
+int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                              const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
+  return skinny_launch(MSR3D_SKINNY_MAX_M, M, K, R, P, ldp, P2, ldp2, njobs, jobs, swiglu, stream);
+}
+
+int msr3d_bf16_skinny_lowrank_wide(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                                   const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
+  return skinny_launch(MSR3D_SKINNY_WIDE_MAX_M, M, K, R, P, ldp, P2, ldp2, njobs, jobs, swiglu, stream);
 }
 
 int msr3d_rope_positions(int B, int T, int H, int D, void *x0, void *x1, const int *pos, const float *cos_td,

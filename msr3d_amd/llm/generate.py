@@ -13,10 +13,11 @@ Four pieces:
                    writes every layer's K / V into the cache; `step` runs one token per live row: per layer RMSNorm,
                    q | k | v as ONE skinny launch, rotation + cache append, decode attention, o, RMSNorm, gate | up with the
                    SwiGLU epilogue, down; then the final norm and the head.  No host synchronisation inside `step`: lengths
-                   and positions live in device memory.
+                   and positions live in device memory.  Up to `max_rows` = 64 live rows (batch x beams).
 * `search`         greedy / beam search with transformers' semantics, written against the engine interface alone
                    (`reserve`, `prefill`, `expand`, `step`, and optionally `select`), so it runs on the CPU with any
-                   engine: that is how its logic is checked exactly against transformers.
+                   engine: that is how its logic is checked exactly against transformers.  A batch with more live rows
+                   than `engine.max_rows` runs as `prompt_groups` of whole prompts, one group after another.
 * `rank_answers`   closed-set answer ranking (the reference's MSR3D.predict_answers): the prompt is prefilled ONCE per
                    row (`prefill(positions="arange")`: the positions of the full forward), the candidate answers run
                    through `CachedDecoder.score` as B x C short suffixes that attend to that one cached prefix
@@ -39,6 +40,12 @@ def _p(t):
 def _call(name, *args):
     rc = getattr(_lib.load(), name)(*args)
     _lib.check(rc, name)
+
+
+def _skinny_entry(M):
+    """The weight-stream product for M live rows: up to 32 the entry every call has used so far (the same bits), the
+    wide one (three or four activation tiles) for 33 .. 64."""
+    return "msr3d_bf16_skinny_lowrank" if M <= 32 else "msr3d_bf16_skinny_lowrank_wide"
 
 
 # ------------------------------------------------------------------------------------------------ selection, in torch
@@ -69,6 +76,24 @@ def torch_select(logits, prev, repetition_penalty, min_length, eos_id, beam_scor
 
 
 # ----------------------------------------------------------------------------------------------------------- search
+def prompt_groups(B, rows_per_prompt, max_rows):
+    """-> [(start, stop), ...]: B prompts of `rows_per_prompt` live rows each as contiguous ranges of whole prompts, the
+    fewest for which every range has at most `max_rows` rows, sizes differing by at most one, the larger ones first."""
+    B, per, cap = int(B), int(rows_per_prompt), int(max_rows)
+    if per < 1 or per > cap:
+        raise ValueError(f"prompt_groups: {per} rows per prompt do not fit {cap} live rows")
+    if B <= 0:
+        return []
+    groups = -(-B // (cap // per))
+    small, extra = divmod(B, groups)
+    out, start = [], 0
+    for g in range(groups):
+        stop = start + small + (1 if g < extra else 0)
+        out.append((start, stop))
+        start = stop
+    return out
+
+
 @torch.no_grad()
 def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=2, pad_id=2, num_beams=1, max_length=256,
            min_length=1, repetition_penalty=1.0, length_penalty=1.0):
@@ -76,7 +101,10 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
     engine: `prefill(inputs_embeds (B, T, H), attention_mask (B, T)) -> (B, V)` logits of the last position,
     `expand(beams)` (every prompt row becomes `beams` adjacent rows), `step(embeds (N, H), beam_idx=None) -> (N, V)`
     (beam_idx (N,): row n continues the cache of row beam_idx[n]); optionally `reserve(rows_per_prompt, new_tokens)`
-    called first and `select(...)` with torch_select's signature.  embed_fn: token ids (N,) -> embeddings (N, H).
+    called first and `select(...)` with torch_select's signature, and `max_rows`: the most live rows (B x num_beams)
+    the engine takes at once -- a larger batch runs as `prompt_groups` of whole prompts one after another, each with its
+    own reserve / prefill / expand, the results concatenated and padded with pad_id to the longest (the one-call
+    result: a prompt's tokens depend on no other prompt).  embed_fn: token ids (N,) -> embeddings (N, H).
     bos_id: its embedding and a mask column of ones are appended to the prompt first (the reference's generate does that
     itself).  Semantics are transformers' (`do_sample=False`, `early_stopping=False`): greedy rows that have emitted eos
     go on as pad_id; beam search keeps 2 x beams candidates a step, scores finished hypotheses
@@ -86,6 +114,17 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
         raise ValueError("num_beams >= 1 and max_length >= 1")
     x, mask = inputs_embeds, attention_mask
     dev = x.device
+    max_rows = getattr(engine, "max_rows", None)
+    if max_rows is not None and x.shape[0] * int(num_beams) > max_rows:
+        # more live rows than the engine takes at once: whole prompts in groups, one after another on the same engine.
+        # A prompt's tokens depend on no other prompt and finished rows are already padded with pad_id, so this is the
+        # one-call result.
+        outs = [search(engine, embed_fn, x[a:b], mask[a:b], bos_id=bos_id, eos_id=eos_id, pad_id=pad_id, num_beams=num_beams,
+                       max_length=max_length, min_length=min_length, repetition_penalty=repetition_penalty,
+                       length_penalty=length_penalty)
+                for a, b in prompt_groups(x.shape[0], int(num_beams), int(max_rows))]
+        width = max(o.shape[1] for o in outs)
+        return torch.cat([torch.nn.functional.pad(o, (0, width - o.shape[1]), value=int(pad_id)) for o in outs], 0)
     if bos_id is not None:
         bos = embed_fn(torch.full((x.shape[0],), int(bos_id), dtype=torch.int64, device=dev)).to(x.dtype)
         x = torch.cat([x, bos[:, None]], 1)
@@ -266,7 +305,10 @@ class KVCache:
 
 # ----------------------------------------------------------------------------------------------------------- engine
 class CachedDecoder:
-    """The decoding engine of a LoRALlamaStack (see the module docstring).  bf16 base weights only."""
+    """The decoding engine of a LoRALlamaStack (see the module docstring).  bf16 base weights only.  At most `max_rows`
+    live rows (batch x beams) per prefill; `search` splits a larger batch into groups of whole prompts."""
+
+    max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
     def __init__(self, stack):
         from .lora import LoRALinear
@@ -302,8 +344,9 @@ class CachedDecoder:
         B, T, Hd = x.shape
         H, D, dev = self.H, self.D, x.device
         beams, new_tokens = self._plan
-        if B * beams > 32:
-            raise ValueError("CachedDecoder: at most 32 live rows (batch x beams)")
+        if B * beams > self.max_rows:
+            raise ValueError(f"CachedDecoder: at most {self.max_rows} live rows (batch x beams), got {B} x {beams}; "
+                             "`search` splits larger batches with prompt_groups")
         mask = attention_mask.to(dev).bool()
         Tp = -(-T // 64) * 64
         if Tp != T:
@@ -462,7 +505,7 @@ class CachedDecoder:
                 jobs[n] = _lib.SkinnyJob(m.weight.data_ptr(), K, b2.data_ptr(), PAD_R,
                                          outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
             with torch.cuda.device(dev):
-                _call("msr3d_bf16_skinny_lowrank", M, K, PAD_R, _p(h), K, _p(u), PAD_R, len(js), jobs, int(swiglu),
+                _call(_skinny_entry(M), M, K, PAD_R, _p(h), K, _p(u), PAD_R, len(js), jobs, int(swiglu),
                       _lib.current_stream_ptr(dev))
         return outs
 
@@ -507,7 +550,7 @@ class CachedDecoder:
         job = (_lib.SkinnyJob * 1)(_lib.SkinnyJob(head.weight.data_ptr(), head.in_features, 0, 0, logits.data_ptr(),
                                                   head.out_features, head.out_features))
         with torch.cuda.device(dev):
-            _call("msr3d_bf16_skinny_lowrank", N, head.in_features, 0, _p(h), head.in_features, _p(None), 0, 1, job, 0,
+            _call(_skinny_entry(N), N, head.in_features, 0, _p(h), head.in_features, _p(None), 0, 1, job, 0,
                   _lib.current_stream_ptr(dev))
         c.len.add_(1)
         c.pos.add_(1)

@@ -156,7 +156,8 @@ class LoRALlamaStack(nn.Module):
         """Greedy / beam search from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py) ->
         (B, <= max_length) int64 generated tokens.  embed_tokens: the (V, hidden) embedding table (or a callable
         ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams, max_length (GENERATED tokens), min_length,
-        repetition_penalty, length_penalty."""
+        repetition_penalty, length_penalty.  Any batch: up to 64 live rows (B x num_beams) decode in one pass, more in
+        groups of whole prompts one after another (the same tokens)."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs)
 

@@ -98,7 +98,8 @@ class MSR3DFullStep(MSR3DHotPath):
         tokens written in and the object mask at their positions (prompt only, no answer) -> one bos embedding and a mask
         column of ones appended -> beam search over the key / value cache (`max_length` counts generated tokens) ->
         id 0 mapped to 2 -> padded with 2 to `max_out_len` -> data_dict['output_tokens'] (B, max_out_len) int64.
-        The prompt may have any length (the engine pads it to the attention kernel's multiple of 64 itself)."""
+        The prompt may have any length (the engine pads it to the attention kernel's multiple of 64 itself) and the batch
+        any size (more than 64 rows = B x num_beams decode in groups of whole prompts)."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if max_length > max_out_len:

@@ -4,7 +4,7 @@ decode step at N live rows x cache length, against (a) the only way to get a tok
 streaming floor: bytes of weights + cache a step must read / 6.29 TB/s (the rate a streaming copy reaches on an MI355X).
 Device events around every repeat (warm-up first, >= 20 repeats): median and spread.  Prints one JSON line.
 
-    python tools/bench_generate.py [--layers 4] [--repeats 20] [--rows 1,5,20] [--lengths 128,320,576]
+    python tools/bench_generate.py [--layers 4] [--repeats 20] [--rows 1,5,20,32,40,64] [--lengths 128,320,576]
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --profile 5x320      # per-kernel, own run
 """
 import argparse
@@ -62,7 +62,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--rows", default="1,5,20")
+    ap.add_argument("--rows", default="1,5,20,32,40,64")
     ap.add_argument("--lengths", default="128,320,576")
     ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
     args = ap.parse_args()
