@@ -55,12 +55,16 @@ def _i(a):
 
 CONTRACTS = {0: "fma(c,c,fma(a,a,b*b))  [LLVM, default]", 1: "(a*a+b*b)+c*c  [no fma]",
              2: "fma(c,c,fma(b,b,a*a))", 3: "fma(a,a,fma(b,b,c*c))",
-             4: "contract 0 + 1 ulp  [envelope, not a contract]", 5: "contract 0 - 1 ulp  [envelope, not a contract]"}
+             4: "contract 0 + 1 ulp  [envelope, not a contract]", 5: "contract 0 - 1 ulp  [envelope, not a contract]",
+             6: "fma(b,b,a*a)+c*c; FPS |p|^2: fma(a,a,b*b)+c*c  [the reference's kernels as hipcc builds them for gfx950]"}
+# the contractions a compiler could really have chosen (4, 5 are an envelope, not a contract)
+REAL_CONTRACTS = (0, 1, 2, 3, 6)
 
 
 def set_contract(c):
     """Floating-point contract of the squared distance a*a + b*b + c*c in FPS / ball query / three_nn
-    (see pn2_oracle.c: sq3).  0 = default = what the HIP kernels are built with."""
+    (see pn2_oracle.c: sq3).  0 = default = what the HIP kernels are built with; 6 = what the reference's own
+    kernels get from hipcc on gfx950 (also switches FPS's |p|^2 and three_interpolate's sum, see pn2_oracle.c)."""
     lib().pn2o_set_contract(int(c))
 
 

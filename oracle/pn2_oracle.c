@@ -12,25 +12,26 @@
  *   src/sampling.cpp, src/ball_query.cpp, src/group_points.cpp,
  *   src/interpolate.cpp.  Each function below cites the lines it follows.
  *
- * PINNING STATUS: the reference's native ops are CUDA-only (every host entry
- * asserts "CPU not supported") and there is no nvcc here, so the reference
- * itself cannot be run.  The reference's only test for this path
- * (pointnet2_test.py:18-33, three_interpolate gradcheck input) is reproduced in
- * tests/; everything else is pinned by known-answer cases derived from the
- * kernel text (tests/test_oracle_kat.py).  For the native ops parity is
- * therefore "unpinned by reference outputs": this restatement DEFINES the
- * contract.  The FPS below is a literal thread-by-thread simulation of the CUDA
- * block (per-thread strided scan + shared-memory halving tree), NOT the
- * closed-form tie-break rule the HIP kernels use, so HIP == oracle also checks
- * that rule.
+ * PINNING STATUS: the reference's host entries are CUDA-only (each asserts "CPU not supported"), but its four
+ * device files compile unmodified as HIP.  oracle/pn2_ref.py builds them for gfx950 from where the reference
+ * lies into oracle/_ref/libpn2_ref.so (never committed), and tests/test_pn2_reference_gpu.py holds every
+ * function below to that build bit for bit, at the floating-point contract that build has (contract 6 below).
+ * The known-answer cases derived from the kernel text stay (tests/test_oracle_kat.py), as does the reference's
+ * only test for this path (pointnet2_test.py:18-33, three_interpolate gradcheck input), reproduced in tests/.
+ * The FPS below is a literal thread-by-thread simulation of the CUDA block (per-thread strided scan +
+ * shared-memory halving tree), NOT the closed-form tie-break rule the HIP kernels use, so HIP == oracle also
+ * checks that rule.
  *
- * Floating-point contract.  nvcc's default (-fmad=true) contracts
+ * Floating-point contract.  The reference spells the squared distance
  *     a*a + b*b + c*c         (a,b,c = coordinate differences)
- * An LLVM-based device compiler contracts the parse tree ((a*a + b*b) + c*c) to
+ * and leaves the contraction to its compiler.  An LLVM-based device compiler contracts the bare expression,
+ * parse tree ((a*a + b*b) + c*c), to
  *     fma(c, c, fma(a, a, b*b))
- * (checked here with hipcc on the reference's literal expression: v_mul b*b,
- * v_fma a, v_fma c).  We pin exactly that chain with explicit fmaf() and build
- * with -ffp-contract=off, so CPU and GPU agree bit-for-bit by construction.
+ * (checked with hipcc on the literal expression alone: v_mul b*b, v_fma a, v_fma c).  That chain is contract 0:
+ * what the shipped HIP kernels spell out and what every golden was made with.  INSIDE the reference's kernels
+ * the same compiler does something else -- the SLP vectoriser packs two of the three products first -- which is
+ * contract 6, read from the disassembly of the cross-check build and pinned by running it.  Every chain here is
+ * explicit fmaf() and the file is built with -ffp-contract=off, so CPU and GPU agree bit-for-bit by construction.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -41,20 +42,27 @@
 #endif
 
 /* (a*a + b*b) + c*c under the floating-point contract in force.  The reference's source spells the sum
- * without parentheses (sampling_gpu.cu:99-104, ball_query_gpu.cu:32-35); which products its compiler fused
- * into fma is not recoverable from the source.  Contract 0 is what an LLVM-based device compiler emits
- * and what the HIP kernels are built with by default; the others are the remaining plausible choices, kept
+ * without parentheses (sampling_gpu.cu:99-104, ball_query_gpu.cu:32-35); which products its compiler fuses
+ * into fma is not in the source.  Contract 0 is what an LLVM-based device compiler emits for the bare
+ * expression and what the HIP kernels are built with by default; 1-3 are the remaining plausible chains, kept
  * so that (a) tools/fma_contract_risk.py can measure how much the choice matters and (b) a vector from an
  * NVIDIA build, should one appear, can be matched by flipping a switch (and MSR3D_SQDIST_CONTRACT in
- * msr3d_amd/csrc/pn2_device.h):
+ * msr3d_amd/csrc/pn2_device.h); 6 is what the reference's kernels really get from hipcc on gfx950:
  *   0  fma(c,c, fma(a,a, b*b))      LLVM contraction of ((a*a + b*b) + c*c)          [default]
  *   1  (a*a + b*b) + c*c            no contraction (-fmad=false)
  *   2  fma(c,c, fma(b,b, a*a))      left product kept, the other two fused
  *   3  fma(a,a, fma(b,b, c*c))      right-to-left chain
  *   4, 5  contract 0 pushed one ulp up / down: NOT a contract -- the envelope of every possible rounding
- *         difference, for the exposure figure of tools/fma_contract_risk.py */
+ *         difference, for the exposure figure of tools/fma_contract_risk.py
+ *   6  the reference's kernels as hipcc (-O3, default contraction) builds them for gfx950.  The vectoriser
+ *      squares two of the three terms in one v_pk_mul_f32, one of them is then fused with the third term's
+ *      square (v_fma_f32) and the other is added last (v_add_f32).  WHICH two are packed differs by expression:
+ *        differences (FPS d, ball query d2, three_nn d):  (x, z) packed  ->  rn(fma(b,b, rn(a*a)) + rn(c*c))
+ *        FPS's |p|^2 (mag, no subtraction in front):      (y, z) packed  ->  rn(fma(a,a, rn(b*b)) + rn(c*c))
+ *      and three_interpolate's three-term sum takes two forms inside ONE launch (see there).  Not shipped: the
+ *      kernels stay on 0, and tests/test_pn2_reference_gpu.py pins this reading to the running build. */
 static int g_contract = 0;
-void pn2o_set_contract(int c) { g_contract = (c >= 0 && c <= 5) ? c : 0; }
+void pn2o_set_contract(int c) { g_contract = (c >= 0 && c <= 6) ? c : 0; }
 int pn2o_get_contract(void) { return g_contract; }
 static inline float sq3(float a, float b, float c) {
   switch (g_contract) {
@@ -63,12 +71,21 @@ static inline float sq3(float a, float b, float c) {
     case 3: return fmaf(a, a, fmaf(b, b, c * c));
     case 4: return nextafterf(fmaf(c, c, fmaf(a, a, b * b)), INFINITY);
     case 5: return nextafterf(fmaf(c, c, fmaf(a, a, b * b)), -INFINITY);
+    case 6: { const float aa = a * a, cc = c * c; const float s = fmaf(b, b, aa); return s + cc; }
     default: return fmaf(c, c, fmaf(a, a, b * b));
   }
 }
 
-/* the squared distance under the contract in force (tests, tools/fma_contract_risk.py) */
+/* FPS's |p|^2 (sampling_gpu.cu:99): the same sum as sq3 under every contract but 6, where the reference
+ * build packs (y, z) instead of (x, z) because no subtraction precedes the squares. */
+static inline float sq3_mag(float a, float b, float c) {
+  if (g_contract == 6) { const float bb = b * b, cc = c * c; const float s = fmaf(a, a, bb); return s + cc; }
+  return sq3(a, b, c);
+}
+
+/* the squared distance / the FPS magnitude under the contract in force (tests, tools/fma_contract_risk.py) */
 float pn2o_sq3(float a, float b, float c) { return sq3(a, b, c); }
+float pn2o_sq3_mag(float a, float b, float c) { return sq3_mag(a, b, c); }
 
 /* include/cuda_utils.h:13-19 -- 2^floor(log2 work) clamped to [1, 512]; the
  * double log/log and the int truncation are kept as written. */
@@ -124,7 +141,7 @@ void pn2o_furthest_point_sampling(int b, int n, int m, const float *xyz, int *id
           const float x2 = dataset[k * 3 + 0];
           const float y2 = dataset[k * 3 + 1];
           const float z2 = dataset[k * 3 + 2];
-          const float mag = sq3(x2, y2, z2);
+          const float mag = sq3_mag(x2, y2, z2);
           if ((double)mag <= 1e-3) continue; /* :100-101, double literal */
           const float d = sq3(x2 - x1, y2 - y1, z2 - z1);
           const float d2 = fminf(d, temp[k]);
@@ -265,9 +282,17 @@ void pn2o_three_nn(int b, int n, int m, const float *unknown, const float *known
 }
 
 /* interpolate_gpu.cu:72-101: points (b,c,m), idx/weight (b,n,3) -> out (b,c,n).
- * (p1*w1 + p2*w2) + p3*w3 contracted like sq3: fma(p3,w3, fma(p1,w1, p2*w2)). */
+ * (p1*w1 + p2*w2) + p3*w3 contracted like sq3: fma(p3,w3, fma(p1,w1, p2*w2)) under contracts 0-5.
+ * Contract 6 (the reference build): the kernel's thread `t` of a block of S = bx*by threads
+ * (opt_block_config(n, c)) walks i = t, t+S, ... < c*n; the loop vectoriser takes those iterations in pairs,
+ * v_pk_mul_f32 / v_pk_fma_f32 / v_pk_fma_f32 = the contract-0 chain, and an odd last iteration falls to the
+ * scalar remainder, v_pk_mul_f32 (p2*w2, p3*w3) / v_fma_f32 / v_add_f32 = rn(fma(p1,w1, rn(p2*w2)) + rn(p3*w3)).
+ * So the rounding of out[l, j] depends on where i = l*n + j falls in its thread's walk. */
 void pn2o_three_interpolate(int b, int c, int m, int n, const float *points, const int *idx,
                             const float *weight, float *out) {
+  int bx = 1, by = 1;
+  if (g_contract == 6) pn2o_opt_block_config(n, c, &bx, &by);
+  const long S = (long)bx * by, total = (long)c * n;
   for (int bi = 0; bi < b; ++bi) {
     const float *P = points + (size_t)bi * m * c;
     const int *I = idx + (size_t)bi * n * 3;
@@ -279,7 +304,19 @@ void pn2o_three_interpolate(int b, int c, int m, int n, const float *points, con
         const float p1 = P[(size_t)l * m + I[j * 3 + 0]];
         const float p2 = P[(size_t)l * m + I[j * 3 + 1]];
         const float p3 = P[(size_t)l * m + I[j * 3 + 2]];
-        O[(size_t)l * n + j] = fmaf(p3, w3, fmaf(p1, w1, p2 * w2));
+        int tail = 0;
+        if (g_contract == 6) {
+          const long i = (long)l * n + j, t = i % S;
+          const long trips = (total - t + S - 1) / S; /* iterations of thread t */
+          tail = (trips & 1) && (i / S == trips - 1);
+        }
+        if (tail) {
+          const float p2w2 = p2 * w2, p3w3 = p3 * w3;
+          const float s = fmaf(p1, w1, p2w2);
+          O[(size_t)l * n + j] = s + p3w3;
+        } else {
+          O[(size_t)l * n + j] = fmaf(p3, w3, fmaf(p1, w1, p2 * w2));
+        }
       }
   }
 }

@@ -1,9 +1,11 @@
-"""How much does the unpinnable floating-point contract of the index ops matter?
+"""How much does the floating-point contract of the index ops matter?
 
 The reference's FPS / ball query compute the squared distance as `x*x + y*y + z*z` in CUDA source
 (_ext_src/src/sampling_gpu.cu:99-104, ball_query_gpu.cu:32-35); which of the products nvcc fuses into fma
 is not recoverable without an NVIDIA toolchain, and this build's oracle + kernels pin ONE choice (contract 0,
-what an LLVM device compiler emits).  This script re-runs the oracle's FPS and ball query under every
+what an LLVM device compiler emits for the bare expression).  Contract 6 is what the reference's own kernels get
+from hipcc on gfx950 (oracle/pn2_ref.py; the vectoriser packs two of the products), the one contraction a user of
+the reference on this hardware really runs.  This script re-runs the oracle's FPS and ball query under every
 plausible contraction (oracle/pn2.py: CONTRACTS) on
 
   * the bench batch (16 scenes x 60 objects x 1024 points = 960 clouds, bench.py's rank-0 batch 0), both
@@ -107,7 +109,7 @@ def run(scenes=16, test_b=64, encoder=True, random_clouds=0):
     base = {}
     names = ["fps1", "ball1", "fps2", "ball2"]
     try:
-        for c in (0, 1, 2, 3, 4, 5):
+        for c in (0, 1, 2, 3, 4, 5, 6):
             pn2.set_contract(c)
             cur = {"bench": index_ops(xyz)}
             for k, v in tests.items():
@@ -136,7 +138,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=16)
     ap.add_argument("--random", type=int, default=4000, help="additional Gaussian clouds (index ops only)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r03_fma_contract_risk.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fma_contract_risk_ref_build.json"))
     a = ap.parse_args()
     res = run(a.scenes, random_clouds=a.random)
     with open(a.out, "w") as f:
