@@ -7,6 +7,7 @@ length from `max_length` and `min_length`, while this library counts generated t
 
     python tests/golden/make_golden_generate.py            # the teacher-forcing fixtures, seed 0
     python tests/golden/make_golden_generate.py gap        # + the free-running fixture (seed search)
+    python tests/golden/make_golden_generate.py longpad    # + the long-prompt fixture
 
 generate_seed0_greedy.npz, generate_seed0_greedy_rep.npz (repetition_penalty 3.0): 3 prompts x 24 positions (row 0
 unpadded, row 1 left-padded, row 2 with masked slots INSIDE the prompt, the last column the bos embedding), 24 new tokens:
@@ -18,6 +19,10 @@ processed scores by its own selection rule; the derivation is checked twice befo
 hypotheses equal transformers' returned sequences, and a teacher-forced fp32 run fed with the derived tokens and beam
 indices reproduces transformers' raw logits of every step to 1e-4.  (Its processed scores are in
 generate_seed0_beam5_scores.npz: one file would exceed the size limit of a committed file.)
+
+generate_longpad_seed0.npz: greedy, 8 new tokens on 3 prompts x 200 positions: row 1 left-padded by 140 (two whole 64-key
+blocks of the attention kernels and part of the third), row 2 with the slots 150 .. 174 masked inside the prompt; the
+prefill crosses three blocks of the cache, the decode steps start at length 200.
 
 generate_gap_seed<S>.npz: the free-running case -- 2 prompts (row 1 left-padded) x GAP_STEPS new tokens, greedy with
 repetition_penalty 3.0, from a seed whose EVERY step has a decision margin of at least M_GAP.  The margin of a
@@ -148,6 +153,15 @@ def gap_fixture(m_gap, seeds=range(GAP_SEED, GAP_SEED + 1), steps=GAP_STEPS):
     raise SystemExit("no seed reaches the margin: search more seeds or shorten the case (never lower M_GAP)")
 
 
+LONGPAD = dict(B=3, T=200, left_pad=140, hole=(150, 175))
+
+
+def longpad_fixture(seed=0, steps=8):
+    model = hf_model(seed)
+    x, keep = prompt(seed, **LONGPAD)
+    greedy_fixture(seed, model, x, keep, 1.0, f"generate_longpad_seed{seed}.npz", steps=steps)
+
+
 def main(seed=0):
     model = hf_model(seed)
     x, keep = prompt(seed)
@@ -159,5 +173,7 @@ def main(seed=0):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "gap":
         gap_fixture(M_GAP)
+    elif len(sys.argv) > 1 and sys.argv[1] == "longpad":
+        longpad_fixture(0)
     else:
         main(0)
