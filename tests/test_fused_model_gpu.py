@@ -15,7 +15,7 @@ def rel(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
 
 
-def _setup(dropout, seed=0, B=3, O=20, E=128, situation_type="as_transform_for_objects"):
+def _setup(dropout, seed=0, B=3, O=20, E=128, situation_type="as_transform_for_objects", lr=1e-3, weight_decay=0.05):
     import msr3d_amd.model  # noqa: F401
     import msr3d_amd.modules  # noqa: F401
     from msr3d_amd import hipops
@@ -35,7 +35,7 @@ def _setup(dropout, seed=0, B=3, O=20, E=128, situation_type="as_transform_for_o
             model.visual_prompter.anchor_size.uniform_(0.5, 1.5)      # (a constant the module never trains)
     params = [p for p in model.parameters() if p.requires_grad]
     dp = FlatGradAllReduce(params, pack_groups=hipops.collect_pack_groups(model))
-    opt = FlatAdamW(dp, lr=1e-3)
+    opt = FlatAdamW(dp, lr=lr, weight_decay=weight_decay)         # (0.05: FlatAdamW's own default)
     assert hipops.attach_packed_views(model, dp, opt) == 3
     assert model._schedule is not None
     model._test_opt = opt

@@ -125,8 +125,9 @@ def test_prefetched_encoder_gives_identical_steps():
     assert run(True) == pytest.approx(run(False), rel=1e-4, abs=1e-6)
 
 
-def _accum_run(accum, use_graph, explicit_grad):
-    """One optimiser step over the SAME 4 scenes, either as one batch or as `accum` micro-batches."""
+def _accum_run(accum, use_graph, explicit_grad, O=10, n_valid=None):
+    """One optimiser step over the SAME 4 scenes, either as one batch or as `accum` micro-batches.
+    n_valid: valid objects per scene (synth_batch's own draw otherwise)."""
     import msr3d_amd.model  # noqa: F401
     import msr3d_amd.modules  # noqa: F401
     from msr3d_amd import hipops
@@ -144,10 +145,12 @@ def _accum_run(accum, use_graph, explicit_grad):
     dp = FlatGradAllReduce(params, pack_groups=hipops.collect_pack_groups(model))
     opt = FlatAdamW(dp, lr=1e-3, weight_decay=0.05, max_grad_norm=5.0)
     hipops.attach_packed_views(model, dp, opt)
-    full = synth_batch(91, 4, O=10, P=1024, device="cuda")
+    full = synth_batch(91, 4, O=O, P=1024, n_valid=n_valid, device="cuda")
+    if n_valid is not None:
+        assert full["obj_masks"].sum(1).tolist() == list(n_valid)
     per = 4 // accum
     micro = [{k: v[i * per:(i + 1) * per].contiguous() for k, v in full.items()} for i in range(accum)]
-    w = torch.randn(4, 10, 128, generator=torch.Generator().manual_seed(1)).cuda()
+    w = torch.randn(4, O, 128, generator=torch.Generator().manual_seed(1)).cuda()
     # the loss weights of the current micro-batch live in STATIC tensors (a captured graph replays
     # fixed addresses; Python-side indexing would be frozen at capture time)
     wi = torch.empty_like(w[:per])
@@ -199,9 +202,15 @@ def test_gradient_accumulation_equals_the_full_batch_step(explicit_grad):
 
 def test_gradient_accumulation_with_the_captured_graph():
     """The graph then holds ONE micro-batch's forward/backward; zeroing, exchange and optimiser run
-    eagerly around accum_steps replays."""
-    ref, _ = _accum_run(2, False, True)
-    got, _ = _accum_run(2, True, True)
+    eagerly around accum_steps replays.  Also on 60-object scenes of 60, 1, 33 and 16 valid objects: the replay of
+    the second micro-batch ([33, 16]) follows a capture and a replay on [60, 1]."""
+    for variant in ({}, {"O": 60, "n_valid": [60, 1, 33, 16]}):
+        _graph_accumulation_equals_eager(**variant)
+
+
+def _graph_accumulation_equals_eager(**variant):
+    ref, _ = _accum_run(2, False, True, **variant)
+    got, _ = _accum_run(2, True, True, **variant)
     # compare the accumulated gradient (Adam's first update is lr * sign(g): entries whose gradient
     # is rounding noise flip sign between two runs of the atomically-summed GEMMs)
     g0, g1 = ref.pop("__flat_grad__").double(), got.pop("__flat_grad__").double()
@@ -357,6 +366,17 @@ def test_window_step_equals_the_accumulated_micro_steps(explicit_grad):
     """micro_batches = m: the whole accumulation window in ONE pass (encoder, trainable part and backward once over
     m x B scenes, loss per micro-batch slice scaled 1/m) == m accumulated micro-steps: same gradient buffer
     (fp32 rounding of a different summation order), same weights after the optimiser step, captured graph."""
+    _window_step_case(explicit_grad, 24, None)
+
+
+@pytest.mark.parametrize("explicit_grad", [False, True])
+def test_window_step_equals_the_accumulated_micro_steps_of_different_padding(explicit_grad):
+    """The same at O = 60 with micro-batches of [60, 60], [17, 48] and [33, 16] valid objects: the accumulated form
+    replays one captured micro-step on three different key masks, the window holds all of them in one pass."""
+    _window_step_case(explicit_grad, 60, [[60, 60], [17, 48], [33, 16]])
+
+
+def _window_step_case(explicit_grad, O, n_valid):
     import msr3d_amd.model  # noqa: F401
     import msr3d_amd.modules  # noqa: F401
     from msr3d_amd import hipops
@@ -366,7 +386,7 @@ def test_window_step_equals_the_accumulated_micro_steps(explicit_grad):
     from msr3d_amd.optim import FlatAdamW
     from msr3d_amd.synth import synth_batch
     from msr3d_amd.train_step import HotPathTrainStep
-    m, B, O, E = 3, 2, 24, 256
+    m, B, E = 3, 2, 256
     w = torch.linspace(-1, 1, B * O * E, device="cuda").view(B, O, E)
     g = w / w.numel()
 
@@ -387,7 +407,10 @@ def test_window_step_equals_the_accumulated_micro_steps(explicit_grad):
                                pack_groups=hipops.collect_pack_groups(model))
         opt = FlatAdamW(dp, lr=1e-3, weight_decay=0.0)
         hipops.attach_packed_views(model, dp, opt)
-        micro = [synth_batch(300 + i, B, O=O, P=1024, device="cuda") for i in range(m)]
+        micro = [synth_batch(300 + i, B, O=O, P=1024, n_valid=n_valid[i] if n_valid else None, device="cuda")
+                 for i in range(m)]
+        if n_valid:
+            assert [b["obj_masks"].sum(1).tolist() for b in micro] == n_valid
         if window:
             whole = {k: torch.cat([b[k] for b in micro], 0) for k in micro[0]}
             step = HotPathTrainStep(model, opt, dp, loss_fn, whole, use_graph=True, micro_batches=m)
