@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 34
+#define MSR3D_ABI_VERSION 35
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -983,17 +983,13 @@ int msr3d_bf16_gemm_batched(int outer, int inner, int M, int N, int K, const voi
                             msr3d_stream_t stream);
 
 /* The row-local / element-wise kernels of one Llama decoder layer (csrc/llm_layer.hip; bf16 storage, fp32
- * arithmetic; transformers.models.llama.modeling_llama: LlamaRMSNorm, apply_rotary_pos_emb, eager attention,
- * LlamaMLP; /root/reference/model/msr3d/msr3d.py:409-415 runs them under bf16 autocast):
+ * arithmetic; transformers.models.llama.modeling_llama: LlamaRMSNorm, apply_rotary_pos_emb, LlamaMLP;
+ * /root/reference/model/msr3d/msr3d.py:409-415 runs them under bf16 autocast):
  *   rmsnorm_fwd   s = x (+ delta) [-> sum_out]; y = w * bf16(s * rsqrt(mean(s^2) + eps)); rstd (M) f32.
  *                 D in {512, 1024, 2048, 4096, 5120, 8192}.
  *   rmsnorm_bwd   dx = rstd * (dy w - xh mean(dy w xh)) (+ dres), xh = s rstd   (w is frozen: no dw)
  *   rope_inplace  x (B, T, H, D) bf16 *= rotation by (cos, sin) (T, D) f32; transpose != 0: the backward
- *   causal_softmax_fwd   probs (B H, T, T) bf16 = softmax over keys t' <= t with key_keep[b][t'] != 0 of fp32 scores
- *   causal_softmax_bwd   dscores bf16 = probs * (dprobs - rowsum(dprobs probs)), dprobs fp32
- *                        (both: T % 4 == 0, T <= 2048, 16-byte aligned fp32 rows)
- *   swiglu_fwd / bwd     h = silu(gate) * up and its two gradients; n % 8 == 0
- *   transpose_bf16       dst[o][i] (cols, rows) = src[o][i] (rows, cols)^T, two-level batch strides (elements) */
+ *   swiglu_fwd / bwd     h = silu(gate) * up and its two gradients; n % 8 == 0 */
 int msr3d_rmsnorm_fwd(int M, int D, const void *x, const void *delta, const void *w, float eps, void *sum_out,
                       void *y, float *rstd, msr3d_stream_t stream);
 int msr3d_rmsnorm_bwd(int M, int D, const void *dy, const void *s, const void *w, const float *rstd,
@@ -1003,16 +999,9 @@ int msr3d_rope_inplace(int B, int T, int H, int D, void *x, const float *cos_td,
 /* the same rotation on TWO tensors of one shape (q and k of a decoder layer) in one launch */
 int msr3d_rope_inplace2(int B, int T, int H, int D, void *x0, void *x1, const float *cos_td, const float *sin_td,
                         int transpose, msr3d_stream_t stream);
-int msr3d_causal_softmax_fwd(int B, int H, int T, const float *scores, const unsigned char *key_keep, void *probs,
-                             msr3d_stream_t stream);
-int msr3d_causal_softmax_bwd(int B, int H, int T, const float *dprobs, const void *probs, void *dscores,
-                             msr3d_stream_t stream);
 int msr3d_swiglu_fwd(long long n, const void *gate, const void *up, void *out, msr3d_stream_t stream);
 int msr3d_swiglu_bwd(long long n, const void *gate, const void *up, const void *dh, void *dgate, void *dup,
                      msr3d_stream_t stream);
-int msr3d_transpose_bf16(int outer, int inner, int rows, int cols, const void *src, int ld_src, long long src_outer,
-                         long long src_inner, void *dst, int ld_dst, long long dst_outer, long long dst_inner,
-                         msr3d_stream_t stream);
 
 /* Causal self-attention of a decoder layer, fused (csrc/llm_attn.hip; transformers' LlamaAttention as the LLM of
  * model/msr3d/msr3d.py:409-415 runs it: softmax(scale q k^T + causal + key padding) v per sequence and head).
@@ -1057,21 +1046,12 @@ int msr3d_fp8_gemm_lowrank_acc(int M, int N, int K, const void *Pq, int ldp, con
                                const float *sq, const void *P2, int ldp2, const void *Q2, int ldq2, void *C, int ldc,
                                msr3d_stream_t stream);
 
-/* out (R, C) fp32 -- or its transpose (C, R) -- += scale * sum_m P[m][r] Q[m][c]: the LoRA weight gradients
- * dA = (s dy B)^T x and dB = dy^T (s x A^T) (peft's lora_A / lora_B, model/msr3d/msr3d.py:103-112; R = 16 or 32).
- * P (M, R), Q (M, C) bf16.  workspace (64 * R * C floats, 16-byte aligned; may be NULL): the row chunks' partial sums
- * are added up in a fixed order by a second launch -- bit-reproducible; without it 16 chunks meet by atomicAdd.
- * accumulate == 0 (workspace only): `out` is overwritten instead of added to -- no zero-fill by the caller. */
-#define MSR3D_LORA_GRAD_CHUNKS 64
-int msr3d_lora_grad(int M, int R, int C, const void *P, int ldp, const void *Q, int ldq, float *out,
-                    int transpose_out, float scale, int accumulate, float *workspace, long long workspace_floats,
-                    msr3d_stream_t stream);
-
-/* dA and dB of one LoRA pair (or one of them: njobs = 1) in ONE launch: job z computes out_z (R, C_z) -- or its
- * transpose (C_z, R) -- (+)= scale * sum_m P_z[m][r] Q_z[m][c] as msr3d_lora_grad does, each workgroup owning 64 output
- * columns over ALL rows (no partial sums, no workspace, bit-reproducible by construction; 236 workgroups for a
- * 4096 / 11008 pair).  accumulate == 0: `out` is overwritten.  C % 8 == 0, ldp / ldq % 8 == 0, P / Q / out 16-byte
- * aligned.  (peft's lora_A / lora_B gradients, model/msr3d/msr3d.py:103-112.) */
+/* The LoRA weight gradients dA = (s dy B)^T x and dB = dy^T (s x A^T) (peft's lora_A / lora_B,
+ * model/msr3d/msr3d.py:103-112; R = 16 or 32), both of one pair (or one of them: njobs = 1) in ONE launch: job z
+ * computes out_z (R, C_z) fp32 -- or its transpose (C_z, R) -- (+)= scale * sum_m P_z[m][r] Q_z[m][c], P_z (M, R),
+ * Q_z (M, C_z) bf16, each workgroup owning 64 output columns over ALL rows (no partial sums, no workspace,
+ * bit-reproducible by construction; 236 workgroups for a 4096 / 11008 pair).  accumulate == 0: `out` is overwritten.
+ * C % 8 == 0, ldp / ldq % 8 == 0, P / Q / out 16-byte aligned. */
 typedef struct {
   int C;
   const void *P; int ldp;      /* (M, R) bf16 */

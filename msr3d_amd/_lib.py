@@ -145,18 +145,12 @@ _SIGNATURES = {
     "msr3d_rmsnorm_bwd": [_c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_rope_inplace": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr],
     "msr3d_rope_inplace2": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
-    "msr3d_causal_softmax_fwd": [_c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr],
-    "msr3d_causal_softmax_bwd": [_c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr],
     "msr3d_swiglu_fwd": [ctypes.c_longlong, _ptr, _ptr, _ptr, _ptr],
     "msr3d_swiglu_bwd": [ctypes.c_longlong, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "msr3d_transpose_bf16": [_c_int, _c_int, _c_int, _c_int, _ptr, _c_int, ctypes.c_longlong, ctypes.c_longlong,
-                             _ptr, _c_int, ctypes.c_longlong, ctypes.c_longlong, _ptr],
     "msr3d_bf16_gemm_skinny": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, _c_float, _ptr],
     "msr3d_bf16_gemm_skinny_quant": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, _c_float, _ptr,
                                      _c_int, _ptr, _ptr],
     "msr3d_colsum_partials": [_c_int, _ptr, _ptr],
-    "msr3d_lora_grad": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int, _c_float, _c_int, _ptr,
-                        ctypes.c_longlong, _ptr],
     "msr3d_lora_grad_pair": [_c_int, _c_int, _c_int, ctypes.POINTER(LoraGradJob), _c_float, _c_int, _ptr],
     "msr3d_lora_shadows": [_c_int, _ptr, _ptr],
     "msr3d_bf16_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, ctypes.POINTER(SkinnyJob),
@@ -278,7 +272,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 34       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 35       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():
@@ -437,6 +431,16 @@ def check(status, what):
 
 def current_stream_ptr(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    """A tensor's data pointer as an entry-point argument; None is NULL."""
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def call(name, *args):
+    """Call entry point `name` of the loaded library; a non-zero status raises."""
+    check(getattr(load(), name)(*args), name)
 
 
 # ---------------------------------------------------------------------------------------

@@ -439,210 +439,6 @@ __global__ __launch_bounds__(512, 1) void bf16_gemm_wide_kernel(const GemmArgs a
   }
 }
 
-// out (R, C) (or its transpose) += scale * sum_m P[m][r] * Q[m][c]      (the LoRA weight gradients: the token
-// reduction of a (M, 16) against a (M, 4096..11008) bf16 matrix).  Bound by reading Q once (19-51 MB), so the rows
-// are cut into enough chunks to put a workgroup on every CU (up to kGradChunks): a lane owns 128 / R adjacent
-// columns (one 16-byte load per row at R = 16) and walks its chunk with R x 8 fp32 accumulators in registers, eight
-// rows' loads in flight; the chunk's P values are broadcast from LDS as float4.  The chunks' partial results go to
-// a workspace as plain stores and a second launch adds them up in chunk order (deterministic; 64 atomicAdds per
-// output element were 4 M memory-side atomics) -- without a workspace: 16 chunks and atomicAdd.
-// (Round 2's column-per-thread kernel, one 2-byte load and 16 LDS reads per row and thread: 112 us at 2304 x 4096.)
-constexpr int kGradChunks = 64, kGradChunksAtomic = 16;
-
-
-template <int R>
-__global__ __launch_bounds__(256) void lora_grad_kernel(int M, int C, const unsigned short *__restrict__ P, int ldp,
-                                                        const unsigned short *__restrict__ Q, int ldq,
-                                                        float *__restrict__ out, int transpose_out, float scale,
-                                                        float *__restrict__ ws) {
-  constexpr int CPL = 128 / R;                         // columns per lane: 8 (R = 16) or 4 (R = 32)
-  constexpr int ROWS = 64;                             // rows of P staged per pass
-  constexpr int PF = 8;                                // rows in flight
-  __shared__ __attribute__((aligned(16))) float ps[ROWS][R];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c0 = (blockIdx.x * 4 + wave) * 64 * CPL + lane * CPL;
-  const int per = (M + gridDim.y - 1) / gridDim.y;
-  const int mb = blockIdx.y * per, me = min(M, mb + per);
-  const bool live = c0 < C;                            // (C is a multiple of CPL: checked by the caller)
-  using qvec = typename std::conditional<CPL == 8, uint4, uint2>::type;
-  float acc[R][CPL];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) acc[r][j] = 0.f;
-  for (int m0 = mb; m0 < me; m0 += ROWS) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < ROWS * R; e += 256) {
-      const int mm = e / R, r = e - mm * R;
-      ps[mm][r] = (m0 + mm < me) ? bf_lo(P[(size_t)(m0 + mm) * ldp + r]) : 0.f;
-    }
-    __syncthreads();
-    if (!live) continue;
-    const int lim = min(ROWS, me - m0);
-    const unsigned short *q = Q + (size_t)m0 * ldq + c0;
-    for (int mb8 = 0; mb8 < lim; mb8 += PF) {
-      qvec v[PF];
-#pragma unroll
-      for (int u = 0; u < PF; ++u)                     // (rows past the chunk re-read its last row: their P is zero)
-        v[u] = *reinterpret_cast<const qvec *>(q + (size_t)min(mb8 + u, lim - 1) * ldq);
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int mm = mb8 + u;                        // (< ROWS: ROWS is a multiple of PF)
-        float qv[CPL];
-        if constexpr (CPL == 8) {
-          qv[0] = bf_lo(v[u].x); qv[1] = bf_hi(v[u].x); qv[2] = bf_lo(v[u].y); qv[3] = bf_hi(v[u].y);
-          qv[4] = bf_lo(v[u].z); qv[5] = bf_hi(v[u].z); qv[6] = bf_lo(v[u].w); qv[7] = bf_hi(v[u].w);
-        } else {
-          qv[0] = bf_lo(v[u].x); qv[1] = bf_hi(v[u].x); qv[2] = bf_lo(v[u].y); qv[3] = bf_hi(v[u].y);
-        }
-        const float live_row = mm < lim ? 1.f : 0.f;
-#pragma unroll
-        for (int r4 = 0; r4 < R; r4 += 4) {
-          const float4 pv = *reinterpret_cast<const float4 *>(&ps[mm][r4]);
-          const float pp[4] = {pv.x * live_row, pv.y * live_row, pv.z * live_row, pv.w * live_row};
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < CPL; ++j) acc[r4 + k][j] = fmaf(pp[k], qv[j], acc[r4 + k][j]);
-        }
-      }
-    }
-  }
-  if (!live) return;
-  if (ws) {                                            // partial (chunk, R, C), plain 16-byte stores
-    float *w = ws + (size_t)blockIdx.y * R * C + c0;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int j = 0; j < CPL; j += 4)
-        *reinterpret_cast<float4 *>(w + (size_t)r * C + j) = make_float4(acc[r][j], acc[r][j + 1], acc[r][j + 2], acc[r][j + 3]);
-    return;
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < CPL; ++j)
-      atomicAdd(out + (transpose_out ? (size_t)(c0 + j) * R + r : (size_t)r * C + c0 + j), acc[r][j] * scale);
-}
-
-// The same reduction on the matrix pipe (round 4; the workspace path).  D[c][r] = sum_m Q[m][c] P[m][r] contracts over
-// the ROW index of both operands, so an MFMA fragment (8 consecutive tokens of one column) is a strided gather: a
-// workgroup stages 64 tokens x 256 columns of Q (and the tokens' R values of P) row-major in LDS with coalesced 16-byte
-// loads -- all of a pass's loads in flight together -- and each wave gathers its fragments with eight 2-byte LDS reads
-// (32 contiguous bytes per 16-lane row group).  4 waves x 64 columns; one v_mfma_f32_16x16x32_bf16 per (column tile,
-// r tile, 32 tokens).  The arithmetic is ~20 k MFMAs per call: the kernel is bound by reading Q once.  Round 3's VALU
-// kernel (a lane = 8 columns x R accumulators, P broadcast from LDS) spent 28 us per 2304 x 4096 call on 128
-// workgroups; the 14 calls of a decoder layer were 14 % of its forward + backward.
-constexpr int kGQ = 256 + 8;       // LDS pitch of a staged Q row, bf16 units (528 B: 16-byte aligned)
-template <int R>
-__global__ __launch_bounds__(256) void lora_grad_mfma_kernel(int M, int C, const unsigned short *__restrict__ P, int ldp,
-                                                             const unsigned short *__restrict__ Q, int ldq,
-                                                             float *__restrict__ ws, int per) {
-  constexpr int RT = R / 16;
-  constexpr int GP = R + 2;                            // LDS pitch of a staged P row (36 / 68 B: 4-byte aligned)
-  __shared__ __attribute__((aligned(16))) unsigned short qs[64 * kGQ];
-  __shared__ __attribute__((aligned(16))) unsigned short ps[64 * GP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = lane & 15, g = lane >> 4;
-  const int cb = blockIdx.x * 256;
-  const int mb = blockIdx.y * per, me = min(M, mb + per);
-  f32x4 acc[4][RT];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int u = 0; u < RT; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // staging roles: Q -- thread t covers 16 bytes (8 columns) of row t / 32 + 8 j; P -- R / 8 chunks of 16 bytes per row
-  const int qrow = tid >> 5, qc = (tid & 31) * 8;
-  const bool qlive = cb + qc < C;                      // (C % 8 == 0: a chunk is inside or outside)
-  constexpr int PCH = R / 8;                           // 16-byte chunks per P row
-  const int prow = tid / PCH, pc = (tid % PCH) * 8;
-  uint4 qv[8], pv;
-  auto fetch = [&](int m0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int m = m0 + qrow + 8 * j;
-      qv[j] = (qlive && m < me) ? *reinterpret_cast<const uint4 *>(Q + (size_t)m * ldq + cb + qc) : make_uint4(0, 0, 0, 0);
-    }
-    const int m = m0 + prow;
-    pv = (prow < 64 && m < me) ? *reinterpret_cast<const uint4 *>(P + (size_t)m * ldp + pc) : make_uint4(0, 0, 0, 0);
-  };
-  fetch(mb);
-  for (int m0 = mb; m0 < me; m0 += 64) {
-    __syncthreads();                                   // the previous pass's fragments have been read
-#pragma unroll
-    for (int j = 0; j < 8; ++j) *reinterpret_cast<uint4 *>(qs + (qrow + 8 * j) * kGQ + qc) = qv[j];
-    if (prow < 64) {
-      unsigned *d = reinterpret_cast<unsigned *>(ps + prow * GP + pc);
-      d[0] = pv.x; d[1] = pv.y; d[2] = pv.z; d[3] = pv.w;
-    }
-    __syncthreads();
-    if (m0 + 64 < me) fetch(m0 + 64);                  // the next pass's loads fly under this pass's gathers
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      const int tk = 32 * sl + 8 * g;                  // this lane's eight tokens
-      bf16x8 fb[RT];
-#pragma unroll
-      for (int u = 0; u < RT; ++u) {
-        union { unsigned short h[8]; bf16x8 v; } w;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) w.h[e] = ps[(tk + e) * GP + 16 * u + i];
-        fb[u] = w.v;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        union { unsigned short h[8]; bf16x8 v; } w;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) w.h[e] = qs[(tk + e) * kGQ + wave * 64 + 16 * t + i];
-#pragma unroll
-        for (int u = 0; u < RT; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.v, fb[u], acc[t][u], 0, 0, 0);
-      }
-    }
-  }
-  // D[c][r]: lane (i, g) of tile (t, u) holds columns c = 16 t + 4 g + q (q = 0..3) of r = 16 u + i
-  float *w = ws + (size_t)blockIdx.y * R * C;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int c = cb + wave * 64 + 16 * t + 4 * g;
-    if (c >= C) continue;                              // (C % 4 == 0)
-#pragma unroll
-    for (int u = 0; u < RT; ++u)
-      *reinterpret_cast<float4 *>(w + (size_t)(16 * u + i) * C + c) = make_float4(acc[t][u][0], acc[t][u][1], acc[t][u][2], acc[t][u][3]);
-  }
-}
-
-// out (+)= scale * sum over the chunks' partials, in chunk order; thread = 4 adjacent columns of one r
-__global__ __launch_bounds__(256) void lora_grad_reduce_kernel(int R, int C, int chunks, const float *__restrict__ ws,
-                                                               float *__restrict__ out, int transpose_out, float scale,
-                                                               int accumulate) {
-  const int e = blockIdx.x * 256 + threadIdx.x;       // over R * C / 4
-  if (e >= R * (C / 4)) return;
-  const int r = e / (C / 4), c = 4 * (e - r * (C / 4));
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float *w = ws + (size_t)r * C + c;
-  constexpr int U = 16;                                // loads in flight (one dependent load per chunk: 19 us)
-  for (int k0 = 0; k0 < chunks; k0 += U) {
-    float4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const float4 *>(w + (size_t)min(k0 + u, chunks - 1) * R * C);
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (k0 + u < chunks) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-  }
-  const float keep = accumulate ? 1.f : 0.f;           // (accumulate == 0: `out` is written, whatever it held)
-  if (transpose_out) {
-    float *o = out + (size_t)c * R + r;
-    const float o0 = accumulate ? o[0] : 0.f, o1 = accumulate ? o[R] : 0.f, o2 = accumulate ? o[2 * R] : 0.f,
-                o3 = accumulate ? o[3 * R] : 0.f;
-    o[0] = o0 * keep + s.x * scale; o[R] = o1 * keep + s.y * scale; o[2 * R] = o2 * keep + s.z * scale;
-    o[3 * R] = o3 * keep + s.w * scale;
-  } else {
-    float4 *o = reinterpret_cast<float4 *>(out + (size_t)r * C + c);
-    float4 t = accumulate ? *o : make_float4(0.f, 0.f, 0.f, 0.f);
-    t.x += s.x * scale; t.y += s.y * scale; t.z += s.z * scale; t.w += s.w * scale;
-    *o = t;
-  }
-}
-
 // dA and dB of ONE LoRA pair in ONE launch, no partial sums at all (round 4 cut the rows into 64 chunks for
 // parallelism, wrote the chunks' partials to a workspace and added them up in a second launch: four launches per pair,
 // 896 a step for a 32-layer stack, 8.5 ms of an 83 ms step; a first one-launch version -- tickets + agent-scope fences, the
@@ -1136,51 +932,6 @@ int msr3d_bf16_gemm_batched(int outer, int inner, int M, int N, int K, const voi
   a.inner = inner;
   a.spo = p_outer; a.spi = p_inner; a.sqo = q_outer; a.sqi = q_inner; a.sco = c_outer; a.sci = c_inner;
   return gemm_dispatch(a, outer * inner, (hipStream_t)stream);
-}
-
-int msr3d_lora_grad(int M, int R, int C, const void *P, int ldp, const void *Q, int ldq, float *out,
-                    int transpose_out, float scale, int accumulate, float *workspace, long long workspace_floats,
-                    msr3d_stream_t stream) {
-  if (M < 0 || C < 0 || (R != 16 && R != 32)) return MSR3D_EINVAL;
-  if (M == 0 || C == 0) return 0;
-  if (!P || !Q || !out || ldp < R || ldq < C) return MSR3D_EINVAL;
-  if (!accumulate && !workspace) return MSR3D_EINVAL;     // (the atomic path can only add)
-  const int cpl = 128 / R;                      // a lane's columns: one 16- / 8-byte load per row
-  if ((C % cpl) || (C % 4) || (ldq % cpl) || (reinterpret_cast<uintptr_t>(Q) & (2 * cpl - 1))) return MSR3D_EINVAL;
-  if (workspace && ((reinterpret_cast<uintptr_t>(workspace) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u)))
-    return MSR3D_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  int chunks;
-  if (workspace && (C % 8) == 0 && (ldq % 8) == 0 && (ldp % 8) == 0 && al16(P) && al16(Q)) {
-    // matrix-pipe kernel: chunks of whole 64-token passes, at most kGradChunks of them
-    int per = (M + kGradChunks - 1) / kGradChunks;
-    per = (per + 63) / 64 * 64;
-    chunks = (M + per - 1) / per;
-    if (workspace_floats < (long long)chunks * R * C) return MSR3D_EINVAL;
-    dim3 grid((C + 255) / 256, chunks);
-    if (R == 16)
-      lora_grad_mfma_kernel<16><<<grid, 256, 0, st>>>(M, C, (const unsigned short *)P, ldp, (const unsigned short *)Q, ldq,
-                                                      workspace, per);
-    else
-      lora_grad_mfma_kernel<32><<<grid, 256, 0, st>>>(M, C, (const unsigned short *)P, ldp, (const unsigned short *)Q, ldq,
-                                                      workspace, per);
-  } else {
-    chunks = (M + 31) / 32;
-    const int cap = workspace ? kGradChunks : kGradChunksAtomic;
-    if (chunks > cap) chunks = cap;
-    if (workspace && workspace_floats < (long long)chunks * R * C) return MSR3D_EINVAL;
-    dim3 grid((C + 256 * cpl - 1) / (256 * cpl), chunks);
-    if (R == 16)
-      lora_grad_kernel<16><<<grid, 256, 0, st>>>(M, C, (const unsigned short *)P, ldp, (const unsigned short *)Q, ldq,
-                                                 out, transpose_out, scale, workspace);
-    else
-      lora_grad_kernel<32><<<grid, 256, 0, st>>>(M, C, (const unsigned short *)P, ldp, (const unsigned short *)Q, ldq,
-                                                 out, transpose_out, scale, workspace);
-  }
-  if (workspace)
-    lora_grad_reduce_kernel<<<(R * (C / 4) + 255) / 256, 256, 0, st>>>(R, C, chunks, workspace, out, transpose_out, scale,
-                                                                       accumulate);
-  return (int)hipGetLastError();
 }
 
 int msr3d_lora_grad_pair(int M, int R, int njobs, const msr3d_lora_grad_job_t *jobs, float scale, int accumulate,

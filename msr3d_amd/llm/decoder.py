@@ -17,21 +17,8 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .._lib import call, current_stream_ptr, ptr
 from .lora import PAD_R, LoRALinear, group_inputs
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _st(dev):
-    return _lib.current_stream_ptr(dev)
-
-
-def _call(name, *args):
-    rc = getattr(_lib.load(), name)(*args)
-    _lib.check(rc, name)
 
 
 class _RMSNormFn(torch.autograd.Function):
@@ -51,8 +38,8 @@ class _RMSNormFn(torch.autograd.Function):
         y = torch.empty_like(x2)
         rstd = torch.empty(M, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _call("msr3d_rmsnorm_fwd", M, D, _p(x2), _p(d2), _p(w), ctypes.c_float(eps),
-                  _p(s) if delta is not None else _p(None), _p(y), _p(rstd), _st(dev))
+            call("msr3d_rmsnorm_fwd", M, D, ptr(x2), ptr(d2), ptr(w), ctypes.c_float(eps),
+                 ptr(s) if delta is not None else ptr(None), ptr(y), ptr(rstd), current_stream_ptr(dev))
         ctx.save_for_backward(s, w, rstd)
         ctx.has_delta = delta is not None
         ctx.shape = x.shape
@@ -67,40 +54,18 @@ class _RMSNormFn(torch.autograd.Function):
         ds2 = ds.reshape(M, D).contiguous() if ds is not None else None
         dx = torch.empty_like(s)
         with torch.cuda.device(dev):
-            _call("msr3d_rmsnorm_bwd", M, D, _p(dy2), _p(s), _p(w), _p(rstd), _p(ds2), _p(dx), _st(dev))
+            call("msr3d_rmsnorm_bwd", M, D, ptr(dy2), ptr(s), ptr(w), ptr(rstd), ptr(ds2), ptr(dx),
+                 current_stream_ptr(dev))
         dx = dx.view(ctx.shape)
         return dx, (dx if ctx.has_delta else None), None, None
 
 
-class _RopeFn(torch.autograd.Function):
-    """Rotary embedding IN PLACE on a projection's output (nothing else reads that tensor: _LoRAFn saves its inputs,
-    not its output), and in place on the incoming gradient in backward: no copies.  Takes the projection's OWN output
-    tensor (tokens, H D) -- not a view of it: an in-place op on a view of a custom function's output is rebased by
-    autograd (CopySlices), which costs two full copies per call in backward (round 4: 128 copies a step)."""
-
-    @staticmethod
-    def forward(ctx, x, cos, sin, B, T, H, D):          # x (B T, H D) or (B, T, H, D) bf16, contiguous
-        if not x.is_contiguous() or x.numel() != B * T * H * D:
-            raise RuntimeError("_RopeFn: a contiguous (B T, H D) tensor expected")
-        with torch.cuda.device(x.device):
-            _call("msr3d_rope_inplace", B, T, H, D, _p(x), _p(cos), _p(sin), 0, _st(x.device))
-        ctx.mark_dirty(x)
-        ctx.save_for_backward(cos, sin)
-        ctx.dims = (B, T, H, D)
-        return x
-
-    @staticmethod
-    def backward(ctx, g):
-        cos, sin = ctx.saved_tensors
-        B, T, H, D = ctx.dims
-        g = g.contiguous()                  # (the attention backward hands over fresh contiguous tensors: no copy)
-        with torch.cuda.device(g.device):
-            _call("msr3d_rope_inplace", B, T, H, D, _p(g), _p(cos), _p(sin), 1, _st(g.device))
-        return g, None, None, None, None, None, None
-
-
 class _Rope2Fn(torch.autograd.Function):
-    """_RopeFn on q AND k in one launch each way (msr3d_rope_inplace2)."""
+    """Rotary embedding IN PLACE on the q and k projections' outputs, one launch each way (msr3d_rope_inplace2), and in
+    place on the incoming gradients in backward: no copies (nothing else reads those tensors: _LoRAFn saves its inputs,
+    not its output).  Takes the projections' OWN output tensors (tokens, H D) -- not views of them: an in-place op on a
+    view of a custom function's output is rebased by autograd (CopySlices), which costs two full copies per call in
+    backward (round 4: 128 copies a step)."""
 
     @staticmethod
     def forward(ctx, q, k, cos, sin, B, T, H, D):
@@ -108,7 +73,8 @@ class _Rope2Fn(torch.autograd.Function):
             if not x.is_contiguous() or x.numel() != B * T * H * D:
                 raise RuntimeError("_Rope2Fn: contiguous (B T, H D) tensors expected")
         with torch.cuda.device(q.device):
-            _call("msr3d_rope_inplace2", B, T, H, D, _p(q), _p(k), _p(cos), _p(sin), 0, _st(q.device))
+            call("msr3d_rope_inplace2", B, T, H, D, ptr(q), ptr(k), ptr(cos), ptr(sin), 0,
+                 current_stream_ptr(q.device))
         ctx.mark_dirty(q, k)
         ctx.save_for_backward(cos, sin)
         ctx.dims = (B, T, H, D)
@@ -120,7 +86,8 @@ class _Rope2Fn(torch.autograd.Function):
         B, T, H, D = ctx.dims
         gq, gk = gq.contiguous(), gk.contiguous()
         with torch.cuda.device(gq.device):
-            _call("msr3d_rope_inplace2", B, T, H, D, _p(gq), _p(gk), _p(cos), _p(sin), 1, _st(gq.device))
+            call("msr3d_rope_inplace2", B, T, H, D, ptr(gq), ptr(gk), ptr(cos), ptr(sin), 1,
+                 current_stream_ptr(gq.device))
         return gq, gk, None, None, None, None, None, None
 
 
@@ -143,8 +110,8 @@ class _AttentionFn(torch.autograd.Function):
         out = torch.empty((B, T, HD), dtype=torch.bfloat16, device=dev)
         lse = torch.empty((B, H, T), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _call("msr3d_attn_fwd", B, T, H, D, _p(q), _p(k), _p(v), HD, _p(keep), ctypes.c_float(scale), _p(out), _p(lse),
-                  _st(dev))
+            call("msr3d_attn_fwd", B, T, H, D, ptr(q), ptr(k), ptr(v), HD, ptr(keep), ctypes.c_float(scale), ptr(out),
+                 ptr(lse), current_stream_ptr(dev))
         ctx.save_for_backward(q, k, v, out, lse, keep)
         ctx.scale = scale
         return out
@@ -159,8 +126,8 @@ class _AttentionFn(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         delta = torch.empty_like(lse)
         with torch.cuda.device(dev):
-            _call("msr3d_attn_bwd", B, T, H, D, _p(q), _p(k), _p(v), _p(out), _p(do), HD, _p(keep), ctypes.c_float(ctx.scale),
-                  _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _st(dev))
+            call("msr3d_attn_bwd", B, T, H, D, ptr(q), ptr(k), ptr(v), ptr(out), ptr(do), HD, ptr(keep),
+                 ctypes.c_float(ctx.scale), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv), current_stream_ptr(dev))
         return dq, dk, dv, None
 
 
@@ -170,7 +137,7 @@ class _SwiGLUFn(torch.autograd.Function):
         gate, up = gate.contiguous(), up.contiguous()
         out = torch.empty_like(gate)
         with torch.cuda.device(gate.device):
-            _call("msr3d_swiglu_fwd", gate.numel(), _p(gate), _p(up), _p(out), _st(gate.device))
+            call("msr3d_swiglu_fwd", gate.numel(), ptr(gate), ptr(up), ptr(out), current_stream_ptr(gate.device))
         ctx.save_for_backward(gate, up)
         return out
 
@@ -180,7 +147,8 @@ class _SwiGLUFn(torch.autograd.Function):
         dh = dh.contiguous()
         dg, du = torch.empty_like(gate), torch.empty_like(up)
         with torch.cuda.device(gate.device):
-            _call("msr3d_swiglu_bwd", gate.numel(), _p(gate), _p(up), _p(dh), _p(dg), _p(du), _st(gate.device))
+            call("msr3d_swiglu_bwd", gate.numel(), ptr(gate), ptr(up), ptr(dh), ptr(dg), ptr(du),
+                 current_stream_ptr(gate.device))
         return dg, du
 
 
@@ -190,6 +158,83 @@ def rope_tables(T, D, theta=10000.0, device=None):
     fr = torch.arange(T, dtype=torch.float32, device=device)[:, None] * inv[None]
     emb = torch.cat([fr, fr], -1)
     return emb.cos().contiguous(), emb.sin().contiguous()
+
+
+class ModuleProducts:
+    """How a walk multiplies a layer's projections.  A products strategy has two operations, both -> (tokens, N) bf16:
+    `project(h, mods)`, the projections `mods` of the same activations h, one tensor each, and `gated(h, gate, up)`,
+    silu(gate(h)) * up(h); and `head(h, lm_head)`, the logits.  This one is the module call (LoRALinear on the tiled
+    GEMMs, _SwiGLUFn, FrozenLinear; differentiable): training, the full forward, `CachedDecoder.prefill` and `.score`.
+    The other is generate.SkinnyProducts, the weight-stream launches of one decode step."""
+
+    @staticmethod
+    def project(h, mods):
+        # forward2d: the autograd function's own output, which the rotation may go on to write in place
+        return [m.forward2d(h) for m in mods]
+
+    @staticmethod
+    def gated(h, gate, up):
+        return _SwiGLUFn.apply(gate(h), up(h))
+
+    @staticmethod
+    def head(h, lm_head):
+        return lm_head(h)
+
+
+def decoder_layer(layer, i, x, delta, attend, products, rows=None):
+    """THE statement of layer `i` of a stack, for every walk (training, prefill, score, step):
+
+        x0 = x + delta; h = RMSNorm(x0); x1 = x0 + o_proj(attend(layer, i, h)); y = down(silu(gate(h2)) * up(h2)),
+        h2 = RMSNorm(x1)                                                      -> (x1, y): the layer's output is x1 + y
+
+    x (..., hidden) bf16; delta: a residual term still to be added to x (the previous layer's y) or None -- the input
+    norm's launch adds it, as the second norm's adds o, so a stack has no stand-alone add kernels either way.
+    attend(layer, i, h) -> context rows (tokens, H D): the attention half, which owns all that differs between the
+    walks -- the q / k / v products, the rotation, the cache write or append, the attention entry.
+    products: how the projections are multiplied (ModuleProducts).
+    rows: a slice of dimension 1 (the LAST layer of a stack whose head only reads those positions): the attention
+    still runs over every token, the second norm and the MLP -- token-local -- only over x[:, rows]."""
+    a, m = layer.self_attn, layer.mlp
+    # (x0 = x + delta; with delta None it is x itself -- and the ONLY use of the layer input from here on, so its
+    # gradient arrives in one piece through the norm's backward)
+    x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
+    o, = products.project(attend(layer, i, h), (a["o_proj"],))
+    if o.dim() != x0.dim():
+        o = o.view(x0.shape)
+    if rows is not None:
+        x0, o = x0[:, rows].contiguous(), o[:, rows].contiguous()
+    x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
+    y, = products.project(products.gated(h2, m["gate_proj"], m["up_proj"]), (m["down_proj"],))
+    return x1, (y if y.dim() == x1.dim() else y.view(x1.shape))
+
+
+def decoder_stack(stack, x, attend, products, rows=None):
+    """THE walk of a LoRALlamaStack: every layer with its MLP output left to the NEXT norm's launch (decoder_layer's
+    `delta`), `rows` selected in the last layer only, the final norm, the head -> logits."""
+    delta, last = None, len(stack.layers) - 1
+    for i, layer in enumerate(stack.layers):
+        x, delta = decoder_layer(layer, i, x, delta, attend, products, rows if i == last else None)
+    if rows is not None and last < 0:
+        x = x[:, rows].contiguous()
+    _, h = _RMSNormFn.apply(x, delta, stack.norm_weight, stack.eps)
+    return products.head(h, stack.lm_head)
+
+
+def causal_attention(attention_mask):
+    """The attention half of training and the full forward: q, k, the rotation of both by their slots 0 .. T-1 in one
+    launch, v, the fused causal attention over all T tokens under the key padding attention_mask (B, T) or None."""
+    keep = None if attention_mask is None else attention_mask.to(torch.uint8).contiguous()     # once, not per layer
+
+    def attend(layer, i, h):
+        B, T, _ = h.shape
+        H, D = layer.num_heads, layer.head_dim
+        a = layer.self_attn
+        cos, sin = layer._tables(T, h.device)
+        q, k = ModuleProducts.project(h, (a["q_proj"], a["k_proj"]))
+        q, k = _Rope2Fn.apply(q, k, cos, sin, B, T, H, D)
+        v, = ModuleProducts.project(h, (a["v_proj"],))
+        return _AttentionFn.apply(q.view(B, T, H, D), k.view(B, T, H, D), v.view(B, T, H, D), keep)
+    return attend
 
 
 class LoRALlamaDecoderLayer(nn.Module):
@@ -239,26 +284,9 @@ class LoRALlamaDecoderLayer(nn.Module):
         (B, T - p, hidden)."""
         if not x.is_cuda:
             raise RuntimeError("LoRALlamaDecoderLayer runs on the GPU only (no CPU fallback)")
-        B, T, Hd = x.shape
-        H, D = self.num_heads, self.head_dim
-        x = x.to(torch.bfloat16)
-        keep = None if attention_mask is None else attention_mask.to(torch.uint8).contiguous()
-        cos, sin = self._tables(T, x.device)
-        a = self.self_attn
-        # (x0 = x + delta; with delta None it is x itself -- and the ONLY use of the layer input from here on, so its
-        # gradient arrives in one piece through the norm's backward)
-        x0, h = _RMSNormFn.apply(x, delta, self.input_layernorm_weight, self.eps)
-        # RoPE in place on the projections' own (tokens, hidden) outputs, not on views of them
-        q, k = _Rope2Fn.apply(a["q_proj"].forward2d(h), a["k_proj"].forward2d(h), cos, sin, B, T, H, D)
-        q, k = q.view(B, T, H, D), k.view(B, T, H, D)
-        v = a["v_proj"](h).view(B, T, H, D)
-        ctx = _AttentionFn.apply(q, k, v, keep)
-        o = a["o_proj"](ctx)
-        if tail_from > 0:
-            x0, o = x0[:, tail_from:].contiguous(), o[:, tail_from:].contiguous()
-        x1, h2 = _RMSNormFn.apply(x0, o, self.post_attention_layernorm_weight, self.eps)
-        m = self.mlp
-        y = m["down_proj"](_SwiGLUFn.apply(m["gate_proj"](h2), m["up_proj"](h2)))
+        x1, y = decoder_layer(self, 0, x.to(torch.bfloat16), delta, causal_attention(attention_mask), ModuleProducts,
+                              slice(tail_from, None) if tail_from > 0 else None)
         if defer_residual:
             return x1, y
         return x1 + y
+

@@ -31,21 +31,29 @@ import math
 import torch
 
 from .. import _lib
+from .._lib import call, current_stream_ptr, ptr
+from .decoder import ModuleProducts, _AttentionFn, decoder_stack, rope_tables
+from .lora import PAD_R, LoRALinear, _skinny, refresh_shadows
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+def _append_bos(embed_fn, x, mask, bos_id):
+    """The embedding of bos_id and a mask column of ones appended to every prompt."""
+    bos = embed_fn(torch.full((x.shape[0],), int(bos_id), dtype=torch.int64, device=x.device)).to(x.dtype)
+    return torch.cat([x, bos[:, None]], 1), torch.cat([mask, torch.ones_like(mask[:, :1])], 1)
 
 
-def _call(name, *args):
-    rc = getattr(_lib.load(), name)(*args)
-    _lib.check(rc, name)
+def _pad_tokens(x, keep, n):
+    """x (..., t, hidden), keep (..., t) bool -> both with n token slots: the n - t appended ones are zero and masked."""
+    t = keep.shape[-1]
+    if n == t:
+        return x, keep
+    return (torch.cat([x, x.new_zeros((*x.shape[:-2], n - t, x.shape[-1]))], -2),
+            torch.cat([keep, keep.new_zeros((*keep.shape[:-1], n - t))], -1))
 
 
-def _skinny_entry(M):
-    """The weight-stream product for M live rows: up to 32 the entry every call has used so far (the same bits), the
-    wide one (three or four activation tiles) for 33 .. 64."""
-    return "msr3d_bf16_skinny_lowrank" if M <= 32 else "msr3d_bf16_skinny_lowrank_wide"
+def _embed_fn(embed_tokens):
+    """embed_tokens: the (V, hidden) table, or already a callable ids -> embeddings."""
+    return embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
 
 
 # ------------------------------------------------------------------------------------------------ selection, in torch
@@ -126,9 +134,7 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
         width = max(o.shape[1] for o in outs)
         return torch.cat([torch.nn.functional.pad(o, (0, width - o.shape[1]), value=int(pad_id)) for o in outs], 0)
     if bos_id is not None:
-        bos = embed_fn(torch.full((x.shape[0],), int(bos_id), dtype=torch.int64, device=dev)).to(x.dtype)
-        x = torch.cat([x, bos[:, None]], 1)
-        mask = torch.cat([mask, torch.ones_like(mask[:, :1])], 1)
+        x, mask = _append_bos(embed_fn, x, mask, bos_id)
     B, nb, L = x.shape[0], int(num_beams), int(max_length)
     if hasattr(engine, "reserve"):
         engine.reserve(nb, L)
@@ -232,9 +238,7 @@ def rank_answers(engine, embed_fn, inputs_embeds, attention_mask, answer_ids, an
     if not bool(am[:, 1].all()):
         raise ValueError("rank_answers: an answer without a real token after bos (its mean loss would be 0 / 0)")
     if bos_id is not None:
-        bos = embed_fn(torch.full((x.shape[0],), first, dtype=torch.int64, device=dev)).to(x.dtype)
-        x = torch.cat([x, bos[:, None]], 1)
-        mask = torch.cat([mask, torch.ones_like(mask[:, :1])], 1)
+        x, mask = _append_bos(embed_fn, x, mask, first)
     B, A = x.shape[0], ids.shape[0]
     C = min(int(num_ans_candidates), A)
     if C < 1:
@@ -295,12 +299,74 @@ class KVCache:
         src, dst = self.kv[self.cur], self.kv[1 - self.cur]
         dev = src.device
         with torch.cuda.device(dev):
-            _call("msr3d_kv_reorder", self.layers * 2, self.rows, self.t_max, self.heads * self.head_dim, _p(src), _p(dst),
-                  _p(idx), _p(self.len), _lib.current_stream_ptr(dev))
+            call("msr3d_kv_reorder", self.layers * 2, self.rows, self.t_max, self.heads * self.head_dim, ptr(src), ptr(dst),
+                 ptr(idx), ptr(self.len), current_stream_ptr(dev))
         il = idx.long()
         for pair in (self._len, self._pos, self._keep):
             torch.index_select(pair[self.cur], 0, il, out=pair[1 - self.cur])
         self.cur = 1 - self.cur
+
+
+# --------------------------------------------------------------------------------------- the products of a decode step
+def _skinny_entry(M):
+    """The weight-stream product for M live rows: up to 32 the entry every call has used so far (the same bits), the
+    wide one (three or four activation tiles) for 33 .. 64."""
+    return "msr3d_bf16_skinny_lowrank" if M <= 32 else "msr3d_bf16_skinny_lowrank_wide"
+
+
+class SkinnyProducts:
+    """decoder.ModuleProducts' operations for the M <= 64 live rows of one decode step: every product streams its weight
+    once (msr3d_bf16_skinny_lowrank), members of one input group share the low-rank activation and ONE launch, gate | up
+    carry the SwiGLU epilogue.  No autograd, bf16 base weights."""
+
+    @staticmethod
+    def project(h, mods, swiglu=False):
+        """The projections `mods` of the same activations h (M, K) -> list of (M, N) bf16 (one tensor with swiglu)."""
+        M, K = h.shape
+        dev = h.device
+        outs, calls = [None] * len(mods), {}
+        for j, m in enumerate(mods):
+            m._sync_weight_t()
+            calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
+        if swiglu and len(calls) != 1:
+            # gate and up without a shared low-rank activation (modules moved to the device after construction leave
+            # their input group): two products and the stand-alone SwiGLU launch
+            gate, up = SkinnyProducts.project(h, mods)
+            act = torch.empty_like(gate)
+            with torch.cuda.device(dev):
+                call("msr3d_swiglu_fwd", gate.numel(), ptr(gate), ptr(up), ptr(act), current_stream_ptr(dev))
+            return [act]
+        for js in calls.values():
+            m0 = mods[js[0]]
+            a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
+            u = torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev)
+            _skinny(M, a_op.shape[0], K, h, a_op, u, PAD_R, m0.scaling, dev)
+            jobs = (_lib.SkinnyJob * len(js))()
+            for n, j in enumerate(js):
+                m = mods[j]
+                b2 = m._shadows(forward=True)[1]
+                if not (swiglu and n == 1):
+                    outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
+                jobs[n] = _lib.SkinnyJob(m.weight.data_ptr(), K, b2.data_ptr(), PAD_R,
+                                         outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
+            with torch.cuda.device(dev):
+                call(_skinny_entry(M), M, K, PAD_R, ptr(h), K, ptr(u), PAD_R, len(js), jobs, int(swiglu),
+                     current_stream_ptr(dev))
+        return outs
+
+    @staticmethod
+    def gated(h, gate, up):
+        return SkinnyProducts.project(h, (gate, up), swiglu=True)[0]
+
+    @staticmethod
+    def head(h, lm_head):
+        lm_head._sync()
+        M, K, V = h.shape[0], lm_head.in_features, lm_head.out_features
+        logits = torch.empty((M, V), dtype=torch.bfloat16, device=h.device)
+        job = (_lib.SkinnyJob * 1)(_lib.SkinnyJob(lm_head.weight.data_ptr(), K, 0, 0, logits.data_ptr(), V, V))
+        with torch.cuda.device(h.device):
+            call(_skinny_entry(M), M, K, 0, ptr(h), K, ptr(None), 0, 1, job, 0, current_stream_ptr(h.device))
+        return logits
 
 
 # ----------------------------------------------------------------------------------------------------------- engine
@@ -311,7 +377,6 @@ class CachedDecoder:
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
     def __init__(self, stack):
-        from .lora import LoRALinear
         self.stack = stack
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
         if any(m.base == "fp8" for m in self.mods):
@@ -335,8 +400,6 @@ class CachedDecoder:
         (what transformers' LlamaModel.forward does when it is called with a mask and no position_ids, i.e. what
         LoRALlamaStack.logits computes: the full forward `score` continues).  The two differ when the prompt has masked
         slots inside it."""
-        from .decoder import _AttentionFn, _RMSNormFn, _SwiGLUFn, rope_tables
-        from .lora import refresh_shadows
         st = self.stack
         if not inputs_embeds.is_cuda:
             raise RuntimeError("CachedDecoder runs on the GPU only (no CPU fallback)")
@@ -347,11 +410,8 @@ class CachedDecoder:
         if B * beams > self.max_rows:
             raise ValueError(f"CachedDecoder: at most {self.max_rows} live rows (batch x beams), got {B} x {beams}; "
                              "`search` splits larger batches with prompt_groups")
-        mask = attention_mask.to(dev).bool()
-        Tp = -(-T // 64) * 64
-        if Tp != T:
-            x = torch.cat([x, torch.zeros((B, Tp - T, Hd), dtype=x.dtype, device=dev)], 1)
-            mask = torch.cat([mask, torch.zeros((B, Tp - T), dtype=torch.bool, device=dev)], 1)
+        Tp = -(-T // 64) * 64                                  # the attention's key tiles; the extra slots are masked
+        x, mask = _pad_tokens(x, attention_mask.to(dev).bool(), Tp)
         x = x.contiguous()
         keep = mask.to(torch.uint8).contiguous()
         if positions == "mask":
@@ -367,28 +427,23 @@ class CachedDecoder:
         self._tables = (cos, sin, rows)
         refresh_shadows(self.mods, False)
         first = slice(0, B * beams, beams)                     # a prompt's first row; expand() fills the others
-        delta, last = None, len(st.layers) - 1
-        for i, layer in enumerate(st.layers):
-            a, m = layer.self_attn, layer.mlp
-            x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
-            q, k, v = a["q_proj"].forward2d(h), a["k_proj"].forward2d(h), a["v_proj"].forward2d(h)
+
+        def attend(layer, i, h):              # q, k, v; the rotation by `pos`; the cache write; the full attention
+            a = layer.self_attn
+            q, k, v = ModuleProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
             with torch.cuda.device(dev):
-                _call("msr3d_rope_positions", B, Tp, H, D, _p(q), _p(k), _p(pos), _p(cos), _p(sin), rows,
-                      _lib.current_stream_ptr(dev))
+                call("msr3d_rope_positions", B, Tp, H, D, ptr(q), ptr(k), ptr(pos), ptr(cos), ptr(sin), rows,
+                     current_stream_ptr(dev))
             q, k, v = q.view(B, Tp, H, D), k.view(B, Tp, H, D), v.view(B, Tp, H, D)
             cache.k(i)[first, :T] = k[:, :T]
             cache.v(i)[first, :T] = v[:, :T]
-            o = a["o_proj"](_AttentionFn.apply(q, k, v, keep))
-            if i == last:                                      # only the last position's logits are wanted
-                x0, o = x0[:, T - 1:T].contiguous(), o[:, T - 1:T].contiguous()
-            x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
-            y = m["down_proj"](_SwiGLUFn.apply(m["gate_proj"](h2), m["up_proj"](h2)))
-            x, delta = x1, y
-        _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
+            return _AttentionFn.apply(q, k, v, keep)
+
+        logits = decoder_stack(st, x, attend, ModuleProducts, slice(T - 1, T))     # only the last position's are wanted
         cache.len[first] = T
         cache.pos[first] = mask.sum(-1).to(torch.int32) if positions == "mask" else T
         cache.keep[first, :T] = keep[:, :T]
-        return st.lm_head(h)[:, 0]
+        return logits[:, 0]
 
     def expand(self, beams):
         c = self.cache
@@ -412,8 +467,6 @@ class CachedDecoder:
         rows alone with the layer forward's kernels; attention is msr3d_attn_prefix_fwd against the cached prefix.  The
         cache is read, never written: `score` may be called again after one `prefill`.  Candidates are walked in chunks of
         at most `max_rows` suffix rows (every row's arithmetic is its own: the result does not depend on the chunking)."""
-        from .decoder import _RMSNormFn, _SwiGLUFn, rope_tables
-        from .lora import refresh_shadows
         st, c = self.stack, self.cache
         if c is None:
             raise RuntimeError("CachedDecoder.score before prefill")
@@ -428,11 +481,7 @@ class CachedDecoder:
             raise ValueError("CachedDecoder.score: 1 .. 64 suffix tokens")
         H, D, HD, dev = self.H, self.D, self.H * self.D, token_embeds.device
         Sp = 16 if S <= 16 else (32 if S <= 32 else 64)         # the kernel's suffix sizes; the extra slots are masked
-        x_all = token_embeds.to(torch.bfloat16)
-        keep_all = token_keep.to(dev).bool()
-        if Sp != S:
-            x_all = torch.cat([x_all, torch.zeros((B, C, Sp - S, Hd), dtype=x_all.dtype, device=dev)], 2)
-            keep_all = torch.cat([keep_all, torch.zeros((B, C, Sp - S), dtype=torch.bool, device=dev)], 2)
+        x_all, keep_all = _pad_tokens(token_embeds.to(torch.bfloat16), token_keep.to(dev).bool(), Sp)
         cos, sin, rows = self._tables
         if rows < c.t_max + Sp:                                # (positions are at most len + Sp - 1 <= t_max + Sp - 1)
             rows = c.t_max + Sp
@@ -443,7 +492,7 @@ class CachedDecoder:
         V = st.lm_head.out_features
         out = torch.empty((B, C, S, V), dtype=torch.bfloat16, device=dev)
         step = max(1, int(max_rows) // (B * Sp))
-        last = len(st.layers) - 1
+        wanted = slice(0, S) if Sp != S else None              # the padded slots' logits are not wanted
         for c0 in range(0, C, step):
             Cc = min(step, C - c0)
             N = B * Cc
@@ -451,68 +500,25 @@ class CachedDecoder:
             skeep = keep_all[:, c0:c0 + Cc].reshape(N, Sp).to(torch.uint8).contiguous()
             pos = (c.pos[:, None, None] + torch.arange(Sp, dtype=torch.int32, device=dev)).expand(B, Cc, Sp)
             pos = pos.reshape(N, Sp).contiguous()
-            delta = None
-            for i, layer in enumerate(st.layers):
-                a, m = layer.self_attn, layer.mlp
-                x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
-                q, k, v = a["q_proj"].forward2d(h), a["k_proj"].forward2d(h), a["v_proj"].forward2d(h)
+
+            def attend(layer, i, h):          # q, k, v; the rotation by `pos`; the suffix rows against the cached prefix
+                a = layer.self_attn
+                q, k, v = ModuleProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
                 ctx = torch.empty((N * Sp, HD), dtype=torch.bfloat16, device=dev)
                 with torch.cuda.device(dev):
-                    s = _lib.current_stream_ptr(dev)
-                    _call("msr3d_rope_positions", N, Sp, H, D, _p(q), _p(k), _p(pos), _p(cos), _p(sin), rows, s)
-                    _call("msr3d_attn_prefix_fwd", B, Cc, Sp, c.t_max, H, D, _p(q), _p(k), _p(v), HD, _p(c.k(i)), _p(c.v(i)),
-                          _p(c.len), _p(c.keep), _p(skeep), ctypes.c_float(scale), _p(ctx), HD, s)
-                o = a["o_proj"](ctx.view(N, Sp, HD))
-                if i == last and Sp != S:                      # the padded slots' logits are not wanted
-                    x0, o = x0[:, :S].contiguous(), o[:, :S].contiguous()
-                x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
-                y = m["down_proj"](_SwiGLUFn.apply(m["gate_proj"](h2), m["up_proj"](h2)))
-                x, delta = x1, y
-            _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
-            out[:, c0:c0 + Cc] = st.lm_head(h).view(B, Cc, S, V)
+                    s = current_stream_ptr(dev)
+                    call("msr3d_rope_positions", N, Sp, H, D, ptr(q), ptr(k), ptr(pos), ptr(cos), ptr(sin), rows, s)
+                    call("msr3d_attn_prefix_fwd", B, Cc, Sp, c.t_max, H, D, ptr(q), ptr(k), ptr(v), HD, ptr(c.k(i)),
+                         ptr(c.v(i)), ptr(c.len), ptr(c.keep), ptr(skeep), ctypes.c_float(scale), ptr(ctx), HD, s)
+                return ctx
+
+            out[:, c0:c0 + Cc] = decoder_stack(st, x, attend, ModuleProducts, wanted).view(B, Cc, S, V)
         return out
 
     # -- one token ------------------------------------------------------------------------------------------------
-    def _products(self, h, mods, swiglu=False):
-        """The projections `mods` of the same activations h (M, K) -> list of (M, N) bf16 (one tensor with swiglu):
-        members of one input group share the low-rank activation and ONE launch."""
-        from .lora import PAD_R, _skinny
-        M, K = h.shape
-        dev = h.device
-        outs, calls = [None] * len(mods), {}
-        for j, m in enumerate(mods):
-            m._sync_weight_t()
-            calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
-        if swiglu and len(calls) != 1:
-            # gate and up without a shared low-rank activation (modules moved to the device after construction leave
-            # their input group): two products and the stand-alone SwiGLU launch
-            gate, up = self._products(h, mods)
-            act = torch.empty_like(gate)
-            with torch.cuda.device(dev):
-                _call("msr3d_swiglu_fwd", gate.numel(), _p(gate), _p(up), _p(act), _lib.current_stream_ptr(dev))
-            return [act]
-        for js in calls.values():
-            m0 = mods[js[0]]
-            a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
-            u = torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev)
-            _skinny(M, a_op.shape[0], K, h, a_op, u, PAD_R, m0.scaling, dev)
-            jobs = (_lib.SkinnyJob * len(js))()
-            for n, j in enumerate(js):
-                m = mods[j]
-                b2 = m._shadows(forward=True)[1]
-                if not (swiglu and n == 1):
-                    outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
-                jobs[n] = _lib.SkinnyJob(m.weight.data_ptr(), K, b2.data_ptr(), PAD_R,
-                                         outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
-            with torch.cuda.device(dev):
-                _call(_skinny_entry(M), M, K, PAD_R, _p(h), K, _p(u), PAD_R, len(js), jobs, int(swiglu),
-                      _lib.current_stream_ptr(dev))
-        return outs
-
     @torch.no_grad()
     def step(self, embeds, beam_idx=None):
         """embeds (N, hidden): the embeddings of the tokens just chosen -> logits (N, V) bf16 of the next position."""
-        from .decoder import _RMSNormFn
         st, c = self.stack, self.cache
         if c is None:
             raise RuntimeError("CachedDecoder.step before prefill")
@@ -526,32 +532,20 @@ class CachedDecoder:
         cos, sin, rows = self._tables
         scale = 1.0 / math.sqrt(D)
         ws = c.workspace
-        delta = None
-        for i, layer in enumerate(st.layers):
-            a, m = layer.self_attn, layer.mlp
-            x0, h = _RMSNormFn.apply(x, delta, layer.input_layernorm_weight, layer.eps)
-            q, k, v = self._products(h, [a["q_proj"], a["k_proj"], a["v_proj"]])
+
+        def attend(layer, i, h):              # q | k | v in one launch; rotation + cache append; the decode attention
+            a = layer.self_attn
+            q, k, v = SkinnyProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
             ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=dev)
             with torch.cuda.device(dev):
-                s = _lib.current_stream_ptr(dev)
-                _call("msr3d_rope_kv_append", N, H, D, c.t_max, _p(q), _p(k), _p(v), HD, _p(c.pos), _p(c.len), _p(cos),
-                      _p(sin), rows, _p(c.k(i)), _p(c.v(i)), s)
-                _call("msr3d_attn_decode", N, c.t_max, H, D, _p(q), HD, _p(c.k(i)), _p(c.v(i)), _p(c.len), 1, _p(c.keep),
-                      ctypes.c_float(scale), _p(ctx), HD, _p(ws), ws.numel() if ws is not None else 0, s)
-            o, = self._products(ctx, [a["o_proj"]])
-            x1, h2 = _RMSNormFn.apply(x0, o, layer.post_attention_layernorm_weight, layer.eps)
-            act = self._products(h2, [m["gate_proj"], m["up_proj"]], swiglu=True)[0]
-            y, = self._products(act, [m["down_proj"]])
-            x, delta = x1, y
-        _, h = _RMSNormFn.apply(x, delta, st.norm_weight, st.eps)
-        head = st.lm_head
-        head._sync()
-        logits = torch.empty((N, head.out_features), dtype=torch.bfloat16, device=dev)
-        job = (_lib.SkinnyJob * 1)(_lib.SkinnyJob(head.weight.data_ptr(), head.in_features, 0, 0, logits.data_ptr(),
-                                                  head.out_features, head.out_features))
-        with torch.cuda.device(dev):
-            _call(_skinny_entry(N), N, head.in_features, 0, _p(h), head.in_features, _p(None), 0, 1, job, 0,
-                  _lib.current_stream_ptr(dev))
+                s = current_stream_ptr(dev)
+                call("msr3d_rope_kv_append", N, H, D, c.t_max, ptr(q), ptr(k), ptr(v), HD, ptr(c.pos), ptr(c.len), ptr(cos),
+                     ptr(sin), rows, ptr(c.k(i)), ptr(c.v(i)), s)
+                call("msr3d_attn_decode", N, c.t_max, H, D, ptr(q), HD, ptr(c.k(i)), ptr(c.v(i)), ptr(c.len), 1, ptr(c.keep),
+                     ctypes.c_float(scale), ptr(ctx), HD, ptr(ws), ws.numel() if ws is not None else 0, s)
+            return ctx
+
+        logits = decoder_stack(st, x, attend, SkinnyProducts)
         c.len.add_(1)
         c.pos.add_(1)
         return logits
@@ -570,21 +564,20 @@ class CachedDecoder:
         tok = torch.empty((N, k), dtype=torch.int32, device=dev)
         bs = None if beam_score is None else beam_score.float().contiguous()
         with torch.cuda.device(dev):
-            _call("msr3d_decode_select", N, V, _p(lg), V, _p(prev), prev.shape[1] if has_prev else 0, _p(n_prev),
-                  ctypes.c_float(repetition_penalty), int(min_length), int(-1 if eos_id is None else eos_id), _p(bs),
-                  int(order), int(k), _p(val), _p(tok), _lib.current_stream_ptr(dev))
+            call("msr3d_decode_select", N, V, ptr(lg), V, ptr(prev), prev.shape[1] if has_prev else 0, ptr(n_prev),
+                 ctypes.c_float(repetition_penalty), int(min_length), int(-1 if eos_id is None else eos_id), ptr(bs),
+                 int(order), int(k), ptr(val), ptr(tok), current_stream_ptr(dev))
         return val, tok
 
 
 @torch.no_grad()
 def generate(stack, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings)."""
-    embed_fn = embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
-    return search(CachedDecoder(stack), embed_fn, inputs_embeds, attention_mask, **search_kwargs)
+    return search(CachedDecoder(stack), _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
 
 
 @torch.no_grad()
 def predict_answers(stack, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs):
     """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder; rank_kwargs: num_ans_candidates, bos_id."""
-    embed_fn = embed_tokens if callable(embed_tokens) else (lambda ids: torch.nn.functional.embedding(ids, embed_tokens))
-    return rank_answers(CachedDecoder(stack), embed_fn, inputs_embeds, attention_mask, answer_ids, answer_mask, **rank_kwargs)
+    return rank_answers(CachedDecoder(stack), _embed_fn(embed_tokens), inputs_embeds, attention_mask, answer_ids, answer_mask,
+                        **rank_kwargs)

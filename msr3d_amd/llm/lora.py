@@ -7,7 +7,8 @@ q/k/v/o/gate/up/down_proj; the LLM runs under bf16 autocast, msr3d.py:409-415).
 `LoRALinear` keeps the frozen weight in bf16 in BOTH orientations (W for the forward, W^T for dx:
 HBM capacity buys a transposing load path away) and fp32 masters of A / B like peft; forward and
 backward are msr3d_bf16_gemm_lowrank (bf16 MFMA, fp32 accumulate) with the low-rank term as one
-extra K step, the weight gradients msr3d_lora_grad.  GPU only (raises on CPU tensors)."""
+extra K step, the weight gradients msr3d_lora_grad_pair (dA and dB in one launch).  GPU only
+(raises on CPU tensors)."""
 import ctypes
 import math
 
@@ -15,27 +16,22 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._lib import call, current_stream_ptr, ptr
 
 PAD_R = 64          # the low-rank pair rides as one extra 64-wide K step (zero-padded)
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
 def _gemm(M, N, K, R, P, ldp, Q, ldq, P2, ldp2, Q2, ldq2, C, ldc, c_f32, scale, dev):
     with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_bf16_gemm_lowrank(M, N, K, R, _p(P), ldp, _p(Q), ldq, _p(P2), ldp2, _p(Q2), ldq2,
-                                                 _p(C), ldc, int(c_f32), ctypes.c_float(scale),
-                                                 _lib.current_stream_ptr(dev))
-    _lib.check(rc, "msr3d_bf16_gemm_lowrank")
+        call("msr3d_bf16_gemm_lowrank", M, N, K, R, ptr(P), ldp, ptr(Q), ldq, ptr(P2), ldp2, ptr(Q2), ldq2, ptr(C), ldc,
+             int(c_f32), ctypes.c_float(scale), current_stream_ptr(dev))
 
 
 def _gemm_acc(M, N, K, R, P, ldp, Q, ldq, P2, ldp2, Q2, ldq2, C, ldc, scale, dev):
     """C (bf16) += the product (msr3d_bf16_gemm_lowrank_acc); -> False where the shape is outside that entry's domain."""
     with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_bf16_gemm_lowrank_acc(M, N, K, R, _p(P), ldp, _p(Q), ldq, _p(P2), ldp2, _p(Q2), ldq2,
-                                                     _p(C), ldc, ctypes.c_float(scale), _lib.current_stream_ptr(dev))
+        rc = _lib.load().msr3d_bf16_gemm_lowrank_acc(M, N, K, R, ptr(P), ldp, ptr(Q), ldq, ptr(P2), ldp2, ptr(Q2), ldq2,
+                                                     ptr(C), ldc, ctypes.c_float(scale), current_stream_ptr(dev))
     if rc == -22:
         return False
     _lib.check(rc, "msr3d_bf16_gemm_lowrank_acc")
@@ -45,9 +41,8 @@ def _gemm_acc(M, N, K, R, P, ldp, Q, ldq, P2, ldp2, Q2, ldq2, C, ldc, scale, dev
 def _skinny(M, N, K, P, Q, C, ldc, scale, dev):
     """C[:, :N] = scale P Q^T, C[:, N:ldc] = 0 (N = r rows of Q)."""
     with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_bf16_gemm_skinny(M, N, K, _p(P), K, _p(Q), K, _p(C), ldc, ldc, ctypes.c_float(scale),
-                                                _lib.current_stream_ptr(dev))
-    _lib.check(rc, "msr3d_bf16_gemm_skinny")
+        call("msr3d_bf16_gemm_skinny", M, N, K, ptr(P), K, ptr(Q), K, ptr(C), ldc, ldc, ctypes.c_float(scale),
+             current_stream_ptr(dev))
 
 
 def _skinny_quant(M, N, K, P, Q, C, ldc, scale, dev):
@@ -55,9 +50,8 @@ def _skinny_quant(M, N, K, P, Q, C, ldc, scale, dev):
     q = torch.empty((M, K), dtype=torch.uint8, device=dev)
     sc = torch.empty((M,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_bf16_gemm_skinny_quant(M, N, K, _p(P), K, _p(Q), K, _p(C), ldc, ldc, ctypes.c_float(scale),
-                                                      _p(q), K, _p(sc), _lib.current_stream_ptr(dev))
-    _lib.check(rc, "msr3d_bf16_gemm_skinny_quant")
+        call("msr3d_bf16_gemm_skinny_quant", M, N, K, ptr(P), K, ptr(Q), K, ptr(C), ldc, ldc, ctypes.c_float(scale),
+             ptr(q), K, ptr(sc), current_stream_ptr(dev))
     return q, sc
 
 
@@ -68,17 +62,15 @@ def quant_rows_fp8(x2):
     q = torch.empty((M, K), dtype=torch.uint8, device=x2.device)
     sc = torch.empty((M,), dtype=torch.float32, device=x2.device)
     with torch.cuda.device(x2.device):
-        rc = _lib.load().msr3d_quant_rows_fp8(M, K, _p(x2), x2.stride(0), _p(q), K, _p(sc), _lib.current_stream_ptr(x2.device))
-    _lib.check(rc, "msr3d_quant_rows_fp8")
+        call("msr3d_quant_rows_fp8", M, K, ptr(x2), x2.stride(0), ptr(q), K, ptr(sc), current_stream_ptr(x2.device))
     return q, sc
 
 
 def _gemm_fp8(M, N, K, Pq, sp, Qq, sq, P2, Q2, C, dev, accumulate=False):
     fn = "msr3d_fp8_gemm_lowrank_acc" if accumulate else "msr3d_fp8_gemm_lowrank"
     with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), fn)(M, N, K, _p(Pq), K, _p(sp), _p(Qq), K, _p(sq), _p(P2), PAD_R, _p(Q2), PAD_R,
-                                      _p(C), N, _lib.current_stream_ptr(dev))
-    _lib.check(rc, fn)
+        call(fn, M, N, K, ptr(Pq), K, ptr(sp), ptr(Qq), K, ptr(sq), ptr(P2), PAD_R, ptr(Q2), PAD_R, ptr(C), N,
+             current_stream_ptr(dev))
 
 
 def _quant_cached(x, x2):
@@ -158,8 +150,7 @@ def refresh_shadows(mods, capturing=False):
             m._shadow_tables = getattr(m, "_shadow_tables", [])
             m._shadow_tables.append(tab)
     with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_lora_shadows(len(jobs), _p(tab), _lib.current_stream_ptr(dev))
-    _lib.check(rc, "msr3d_lora_shadows")
+        call("msr3d_lora_shadows", len(jobs), ptr(tab), current_stream_ptr(dev))
     for m in stale:
         m._shadow_key = "captured" if capturing else m._pair_key()
 
@@ -270,7 +261,6 @@ class _LoRAFn(torch.autograd.Function):
                 rec[4] += 1
                 if rec[4] >= rec[5]:           # the last member of THIS backward pass: a second pass over the same graph
                     rec[3], rec[4] = None, 0   # (retain_graph) starts with a buffer of its own
-        lib = _lib.load()
         # On the flat-gradient engine (dp.py) the pair's .grad are views of the flat buffer: the kernels ADD into them
         # (accumulate = 1) and report readiness themselves -- no AccumulateGrad add launch per parameter (448 a step for
         # a 32-layer stack) and no temporaries.
@@ -284,14 +274,13 @@ class _LoRAFn(torch.autograd.Function):
             dB = torch.empty((N, r), dtype=torch.float32, device=dev)
             acc = 0
         with torch.cuda.device(dev):
-            st = _lib.current_stream_ptr(dev)
+            st = current_stream_ptr(dev)
             # dA = (s dy B)^T x = v^T x ; dB = dy^T (s x A^T) = dy^T u   (s already inside u and v): both in ONE launch,
             # a workgroup per 64 output columns over all tokens -- no partial sums, no workspace
             jobs = (_lib.LoraGradJob * 2)(
                 _lib.LoraGradJob(K, v.data_ptr(), PAD_R, x2.data_ptr(), K, dA.data_ptr(), 0),
                 _lib.LoraGradJob(N, u.data_ptr() + 2 * ctx.u_col, PAD_R, dy2.data_ptr(), N, dB.data_ptr(), 1))
-            rc = lib.msr3d_lora_grad_pair(M, r, 2, jobs, ctypes.c_float(1.0), acc, st)
-            _lib.check(rc, "msr3d_lora_grad_pair")
+            call("msr3d_lora_grad_pair", M, r, 2, jobs, ctypes.c_float(1.0), acc, st)
         if direct is not None:
             hipops._direct_done(direct)
             return dx, None, None, None

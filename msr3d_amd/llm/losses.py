@@ -1,17 +1,11 @@
 """`loss (B,)` of /root/reference/model/msr3d/msr3d.py:426-441 -- the mean cross-entropy of each
 sequence over its supervised tokens -- as one autograd node over msr3d_seq_ce_fwd / _bwd."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
-from .. import _lib
+from .._lib import call, current_stream_ptr, ptr
 
 _DTYPE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class _SeqCE(torch.autograd.Function):
@@ -26,9 +20,8 @@ class _SeqCE(torch.autograd.Function):
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
         count = torch.empty((B,), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.load().msr3d_seq_ce_fwd(B, T, V, _p(x), _DTYPE[x.dtype], _p(tg), _p(lse), _p(tok), _p(loss),
-                                              _p(count), _lib.current_stream_ptr(dev))
-        _lib.check(rc, "msr3d_seq_ce_fwd")
+            call("msr3d_seq_ce_fwd", B, T, V, ptr(x), _DTYPE[x.dtype], ptr(tg), ptr(lse), ptr(tok), ptr(loss), ptr(count),
+                 current_stream_ptr(dev))
         ctx.save_for_backward(x, tg, lse, count)
         return loss
 
@@ -39,9 +32,8 @@ class _SeqCE(torch.autograd.Function):
         dx = torch.empty_like(x)
         gg = g.to(torch.float32).contiguous()
         with torch.cuda.device(x.device):
-            rc = _lib.load().msr3d_seq_ce_bwd(B, T, V, _p(x), _DTYPE[x.dtype], _p(tg), _p(lse), _p(count), _p(gg),
-                                              _p(dx), _lib.current_stream_ptr(x.device))
-        _lib.check(rc, "msr3d_seq_ce_bwd")
+            call("msr3d_seq_ce_bwd", B, T, V, ptr(x), _DTYPE[x.dtype], ptr(tg), ptr(lse), ptr(count), ptr(gg), ptr(dx),
+                 current_stream_ptr(x.device))
         return dx, None
 
 

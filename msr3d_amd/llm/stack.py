@@ -14,21 +14,14 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .decoder import LoRALlamaDecoderLayer, _RMSNormFn
-from .lora import LoRALinear, refresh_shadows
+from .decoder import LoRALlamaDecoderLayer, ModuleProducts, causal_attention, decoder_stack
+from .lora import LoRALinear, _gemm as _lora_gemm, refresh_shadows
 from .losses import seq_mean_cross_entropy
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
 def _gemm(M, N, K, P, Q, C, dev):
-    """C (M, N) bf16 = P (M, K) Q (N, K)^T, bf16 operands."""
-    with torch.cuda.device(dev):
-        rc = _lib.load().msr3d_bf16_gemm_lowrank(M, N, K, 0, _p(P), K, _p(Q), K, None, 0, None, 0, _p(C), N, 0,
-                                                 ctypes.c_float(1.0), _lib.current_stream_ptr(dev))
-    _lib.check(rc, "msr3d_bf16_gemm_lowrank")
+    """C (M, N) bf16 = P (M, K) Q (N, K)^T, bf16 operands: lora._gemm without a low-rank term."""
+    _lora_gemm(M, N, K, 0, P, K, Q, K, None, 0, None, 0, C, N, 0, 1.0, dev)
 
 
 class _FrozenLinearFn(torch.autograd.Function):
@@ -56,10 +49,9 @@ class _FrozenLinearFn(torch.autograd.Function):
             # as a batch with fp32 partials puts 10 x as many workgroups on it, the partials are added in chunk order
             part = torch.empty((S, M, K), dtype=torch.float32, device=dy.device)
             with torch.cuda.device(dy.device):
-                rc = _lib.load().msr3d_bf16_gemm_batched(S, 1, M, K, N // S, _p(dy2), N, N // S, 0, _p(mod.weight_t), N, N // S, 0,
-                                                         _p(part), K, M * K, 0, 1, ctypes.c_float(1.0),
-                                                         _lib.current_stream_ptr(dy.device))
-            _lib.check(rc, "msr3d_bf16_gemm_batched")
+                _lib.call("msr3d_bf16_gemm_batched", S, 1, M, K, N // S, _lib.ptr(dy2), N, N // S, 0, _lib.ptr(mod.weight_t),
+                          N, N // S, 0, _lib.ptr(part), K, M * K, 0, 1, ctypes.c_float(1.0),
+                          _lib.current_stream_ptr(dy.device))
             dx = part.sum(0).to(torch.bfloat16)
         else:
             dx = torch.empty((M, K), dtype=torch.bfloat16, device=dy.device)
@@ -128,29 +120,23 @@ class LoRALlamaStack(nn.Module):
         """from_position = p: only the logits of positions p .. T-1 (B, T - p, V) -- the attention of every layer still runs
         over all T tokens; the LAST layer's token-local half (second norm + MLP), the final norm and the head only over that
         tail (nothing else ever reads the other rows of those)."""
+        if not inputs_embeds.is_cuda:
+            raise RuntimeError("LoRALlamaStack runs on the GPU only (no CPU fallback)")
         x = inputs_embeds.to(torch.bfloat16)
         # the bf16 images of all 7 x layers LoRA pairs: ONE launch per optimiser step (224 pairs x 4 copies before)
         mods = self._pairs()
         capturing = x.is_cuda and torch.cuda.is_current_stream_capturing()
         refresh_shadows(mods, capturing)
-        keep = None if attention_mask is None else attention_mask.to(torch.uint8).contiguous()     # once, not per layer
         for m in mods:
             m._fresh_in_capture = capturing
         try:
-            delta = None
-            last = len(self.layers) - 1
-            for i, layer in enumerate(self.layers):
-                # the residual sum x + mlp(x) is left to the NEXT layer's input norm (one fused launch, no add kernel);
-                # the last layer's token-local half (second norm + MLP) only over the positions the head reads
-                x, delta = layer(x, attention_mask=keep, delta=delta, defer_residual=True,
-                                 tail_from=from_position if i == last else 0)
-            if from_position > 0 and not self.layers:
-                x = x[:, from_position:].contiguous()
-            _, h = _RMSNormFn.apply(x, delta, self.norm_weight, self.eps)
+            # the last layer's token-local half (second norm + MLP), the final norm and the head only over the positions
+            # the caller reads
+            return decoder_stack(self, x, causal_attention(attention_mask), ModuleProducts,
+                                 slice(from_position, None) if from_position > 0 else None)
         finally:
             for m in mods:
                 m._fresh_in_capture = False
-        return self.lm_head(h)
 
     def generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
         """Greedy / beam search from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py) ->

@@ -196,22 +196,7 @@ def test_rope_is_the_reference_rotation_and_its_transpose():
 
 def test_causal_softmax_and_swiglu_vs_float64():
     from msr3d_amd import _lib
-    B, H, T = 2, 3, 128
     st = _lib.current_stream_ptr(torch.device("cuda"))
-    S = torch.randn(B, H, T, T, device="cuda") * 3
-    keep = torch.ones(B, T, dtype=torch.uint8, device="cuda")
-    keep[1, :20] = 0
-    P = torch.empty(B, H, T, T, dtype=torch.bfloat16, device="cuda")
-    _call("msr3d_causal_softmax_fwd", B, H, T, _p(S), _p(keep), _p(P), st)
-    vis = torch.tril(torch.ones(T, T, dtype=torch.bool, device="cuda"))[None, None] & keep.bool()[:, None, None, :]
-    want = torch.softmax(S.double().masked_fill(~vis, float("-inf")), -1).nan_to_num(0.0)
-    assert rel(P, want) < 3e-3
-    assert float(P.float()[1, :, :20].abs().max()) == 0.0            # rows with no visible key: zeros
-    dP = torch.randn(B, H, T, T, device="cuda")
-    dS = torch.empty_like(P)
-    _call("msr3d_causal_softmax_bwd", B, H, T, _p(dP), _p(P), _p(dS), st)
-    Pd = P.double()
-    assert rel(dS, Pd * (dP.double() - (dP.double() * Pd).sum(-1, keepdim=True))) < 4e-3
     n = 4096 * 24
     gte, up, dh = (torch.randn(n, device="cuda").bfloat16() for _ in range(3))
     out, dg, du = torch.empty_like(gte), torch.empty_like(gte), torch.empty_like(gte)
@@ -238,9 +223,6 @@ def test_batched_gemm_and_transpose():
           ctypes.c_float(0.5), st)
     want = 0.5 * torch.einsum("bthd,bshd->bhts", q.double(), k.double())
     assert rel(S, want) < 1e-5
-    vt = torch.empty(B, H, D, T, dtype=torch.bfloat16, device="cuda")
-    _call("msr3d_transpose_bf16", B, H, T, D, _p(k), HD, T * HD, D, _p(vt), T, H * D * T, D * T, st)
-    assert torch.equal(vt, k.permute(0, 2, 3, 1).contiguous())
 
 
 @pytest.mark.parametrize("M", [2304, 2000])
