@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 35
+#define MSR3D_ABI_VERSION 36
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1112,12 +1112,31 @@ int msr3d_lora_shadows(int njobs, const msr3d_lora_shadow_job_t *jobs_device, ms
  *   processors = repetition penalty over prev_tokens[n][0 .. n_prev[n] - 1] (int64, row stride ld_prev; x < 0 ? x p : x / p,
  *   once per distinct token) then eos_id -> -inf while n_prev[n] < min_length.  beam_score NULL = 0; n_prev NULL = 0.
  *   V <= MSR3D_DECODE_SELECT_MAX_V (the row lives in LDS as fp32), k <= MSR3D_DECODE_SELECT_MAX_K.  out_val, out_tok (N, k).
+ * msr3d_decode_sample (csrc/llm_sample.hip): per row n, k draws without replacement from softmax(w[n]):
+ *   s = the processors of msr3d_decode_select in its two orders, WITHOUT beam_score; s / temperature; top_k (0 = off, and
+ *   off when >= V): entries below the max(top_k, min_keep)-th largest value -> -inf, ties at that value all stay; top_p
+ *   (1 = off): in ascending (score, token id) order -- equal scores ordered as a stable sort orders them, the lower id
+ *   first -- every entry whose running softmax probability is <= 1 - top_p -> -inf, except the last min_keep (the
+ *   threshold is 1 - the fp32 top_p this entry receives, taken in double: 0.10000002 for 0.9f; the running probability is
+ *   fixed point, exp(s - max) 2^40 summed in 64-bit integers, compared with floor(threshold x total) computed once in
+ *   double);
+ *   order 0: w = log_softmax(s);  order 1: w = s + beam_score[n]  (no renormalisation: the beams of a prompt share one
+ *   softmax).  key = w + g, g = -log(-log u) Gumbel noise; the k largest keys in descending order, ties to the lower
+ *   token, are k successive draws.  out_key, out_val (= w at the token), out_tok (N, k); a row with fewer than k
+ *   entries left gives key = val = -inf, tok = -1 in the rest.  noise (N, V) fp32 with row stride ld_noise supplies g
+ *   (a test seam); NULL: u = (bits + 0.5) 2^-24 from a 24-bit counter hash of (seed, step, row0 + n, token) -- no state,
+ *   the same bits for the same arguments whatever the launch's N.  The cut is found without a sort and without float
+ *   atomics (integer histograms, fixed-point mass): bit-reproducible.  V <= MSR3D_DECODE_SAMPLE_MAX_V (the row in LDS
+ *   beside 3 KB of histograms), k <= MSR3D_DECODE_SELECT_MAX_K, temperature > 0, 0 < top_p <= 1, top_k >= 0,
+ *   1 <= min_keep <= V, seed, step, row0 >= 0.
+ * msr3d_gumbel_noise: out (N, V) fp32 with row stride ld = the g msr3d_decode_sample generates for these arguments.
  * ------------------------------------------------------------------------- */
 #define MSR3D_SKINNY_MAX_M 32
 #define MSR3D_SKINNY_WIDE_MAX_M 64
 #define MSR3D_ATTN_DECODE_MAX_SPLITS 8
 #define MSR3D_DECODE_SELECT_MAX_V 40000
 #define MSR3D_DECODE_SELECT_MAX_K 64
+#define MSR3D_DECODE_SAMPLE_MAX_V 39936
 typedef struct {
   const void *W; int ldw;      /* (N, K) bf16 */
   const void *B2; int ldb2;    /* (N, R) bf16 or NULL */
@@ -1142,6 +1161,12 @@ int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src
 int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,
                         const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
                         int order, int k, float *out_val, int *out_tok, msr3d_stream_t stream);
+int msr3d_decode_sample(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,
+                        const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
+                        int order, int k, float temperature, int top_k, float top_p, int min_keep, const float *noise,
+                        int ld_noise, long long seed, int step, int row0, float *out_key, float *out_val, int *out_tok,
+                        msr3d_stream_t stream);
+int msr3d_gumbel_noise(int N, int V, long long seed, int step, int row0, float *out, int ld, msr3d_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Prefix-shared attention (csrc/llm_attn.hip; CachedDecoder.score, closed-set answer ranking): C candidate suffixes of

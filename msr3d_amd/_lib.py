@@ -166,6 +166,10 @@ _SIGNATURES = {
     "msr3d_kv_reorder": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_decode_select": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,
                             _c_int, _ptr, _ptr, _ptr],
+    "msr3d_decode_sample": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,
+                            _c_int, _c_float, _c_int, _c_float, _c_int, _ptr, _c_int, ctypes.c_longlong, _c_int, _c_int,
+                            _ptr, _ptr, _ptr, _ptr],
+    "msr3d_gumbel_noise": [_c_int, _c_int, ctypes.c_longlong, _c_int, _c_int, _ptr, _c_int, _ptr],
     "msr3d_attn_prefix_order": [_c_int],
     "msr3d_attn_prefix_fwd": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr,
                               _ptr, _c_float, _ptr, _c_int, _ptr],
@@ -272,7 +276,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 35       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 36       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():

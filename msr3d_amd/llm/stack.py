@@ -139,11 +139,14 @@ class LoRALlamaStack(nn.Module):
                 m._fresh_in_capture = False
 
     def generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
-        """Greedy / beam search from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py) ->
-        (B, <= max_length) int64 generated tokens.  embed_tokens: the (V, hidden) embedding table (or a callable
-        ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams, max_length (GENERATED tokens), min_length,
-        repetition_penalty, length_penalty.  Any batch: up to 64 live rows (B x num_beams) decode in one pass, more in
-        groups of whole prompts one after another (the same tokens)."""
+        """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
+        -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
+        (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
+        max_length (GENERATED tokens), min_length, repetition_penalty, length_penalty, and do_sample, top_p, top_k,
+        temperature, num_return_sequences, seed, draw (`search` states them: nucleus / top-k sampling and beam sampling
+        with transformers' semantics, drawn by msr3d_decode_sample from counter noise -- the same seed, the same tokens).
+        Any batch: up to 64 live rows (B x max(num_beams, num_return_sequences)) decode in one pass, more in groups of
+        whole prompts one after another (the same tokens)."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs)
 

@@ -10,9 +10,10 @@
 
 What is NOT here (out of SURVEY §8's scope): tokenizer and prompt assembly (the step takes
 token ids), the 2D image branch (`image_encoder`, `llm_proj_img`: one placeholder token per sequence), CLIP fusion, and of the reference's `generate`
-everything but greedy / beam search: nucleus sampling, `num_captions > 1`, `pred_action`.
+only `pred_action`.
 `MSR3DFullStep.generate` is the reference's evaluation path (msr3d.py:445-524): prompt embeddings + scene tokens + one bos
-embedding -> KV-cached beam search (msr3d_amd/llm/generate.py) -> `output_tokens`.  `MSR3DFullStep.predict_answers` is
+embedding -> KV-cached greedy / beam search, nucleus sampling or beam sampling, `num_captions` results per prompt
+(msr3d_amd/llm/generate.py) -> `output_tokens`.  `MSR3DFullStep.predict_answers` is
 its closed-vocabulary path (msr3d.py:526-655): the same prompt, prefilled once, and the candidate answers scored as
 short suffixes on that one cache (`rank_answers`) -> `answers_id`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
 under `llm_model.*` (msr3d_amd/llm/checkpoint.py maps Hugging Face / peft keys onto it).
@@ -93,13 +94,21 @@ class MSR3DFullStep(MSR3DHotPath):
 
     @torch.no_grad()
     def generate(self, data_dict, num_beams=5, max_length=256, min_length=1, repetition_penalty=3.0, length_penalty=1.0,
-                 max_out_len=256, bos_id=1, eos_id=2):
-        """The reference's MSR3D.generate with `use_nucleus_sampling=False`: hot path -> prompt embeddings with the scene
-        tokens written in and the object mask at their positions (prompt only, no answer) -> one bos embedding and a mask
-        column of ones appended -> beam search over the key / value cache (`max_length` counts generated tokens) ->
-        id 0 mapped to 2 -> padded with 2 to `max_out_len` -> data_dict['output_tokens'] (B, max_out_len) int64.
+                 max_out_len=256, bos_id=1, eos_id=2, use_nucleus_sampling=False, top_p=0.9, temperature=1.0,
+                 num_captions=1, seed=None, top_k=50):
+        """The reference's MSR3D.generate: hot path -> prompt embeddings with the scene tokens written in and the object
+        mask at their positions (prompt only, no answer) -> one bos embedding and a mask column of ones appended -> beam
+        search (or sampling) over the key / value cache (`max_length` counts generated tokens) -> id 0 mapped to 2 ->
+        padded with 2 to `max_out_len` -> data_dict['output_tokens'] (B x num_captions, max_out_len) int64, a prompt's
+        captions in adjacent rows.
+        use_nucleus_sampling = transformers' `do_sample`: with num_beams == 1 every caption is sampled token by token,
+        with num_beams > 1 it is beam sampling; `top_p`, `temperature` and `top_k` act only then.  top_k: the reference
+        never passes it, and the transformers it pins (4.28.1) then takes 50 whenever it samples -- so 50 is what the
+        reference's sampled captions are drawn from and the default here; top_k=0 gives pure nucleus sampling.
+        num_captions = `num_return_sequences`: the n best beams, or n samples per prompt.  seed: the draw's counter seed
+        (None: 63 bits from torch's CPU generator, so torch.manual_seed makes a call reproducible).
         The prompt may have any length (the engine pads it to the attention kernel's multiple of 64 itself) and the batch
-        any size (more than 64 rows = B x num_beams decode in groups of whole prompts)."""
+        any size (more than 64 rows = B x max(num_beams, num_captions) decode in groups of whole prompts)."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if max_length > max_out_len:
@@ -119,7 +128,9 @@ class MSR3DFullStep(MSR3DHotPath):
         scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
         out = self.llm_model.generate(emb, am, self.embed_tokens, bos_id=bos_id, eos_id=eos_id, pad_id=eos_id,
                                       num_beams=num_beams, max_length=max_length, min_length=min_length,
-                                      repetition_penalty=repetition_penalty, length_penalty=length_penalty)
+                                      repetition_penalty=repetition_penalty, length_penalty=length_penalty,
+                                      do_sample=bool(use_nucleus_sampling), top_p=top_p, top_k=top_k,
+                                      temperature=temperature, num_return_sequences=num_captions, seed=seed)
         out = torch.where(out == 0, torch.full_like(out, 2), out)
         pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
         d["output_tokens"] = torch.cat([out, pad], 1)

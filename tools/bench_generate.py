@@ -6,6 +6,7 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
 
     python tools/bench_generate.py [--layers 4] [--repeats 20] [--rows 1,5,20,32,40,64] [--lengths 128,320,576]
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --profile 5x320      # per-kernel, own run
+    python tools/bench_generate.py --sample      # the draw kernel beside the select kernel and a decode step
 """
 import argparse
 import json
@@ -58,8 +59,42 @@ def step_bytes(layers, rows, length):
     return layers * (per_layer + cache) + 2 * HIDDEN * VOCAB
 
 
+def sample_cells(args):
+    """--sample: one msr3d_decode_sample launch beside one msr3d_decode_select launch on the same logits (8 previous
+    tokens, repetition penalty 3), and a decode step followed by either, at the two shapes decoding has: 64 rows drawing
+    one token (sampling without beams) and 5 prompts x 5 beams drawing 2 x beams candidates (beam sampling)."""
+    net = build(args.layers)
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    out = {"bench": "generate_sample", "device": torch.cuda.get_device_name(0), "layers": args.layers, "vocab": VOCAB,
+           "repeats": args.repeats, "cells": []}
+    for rows, k, order in ((64, 1, 0), (25, 10, 1)):
+        lg = (torch.randn(rows, VOCAB, generator=gen, device="cuda") * 3.0).to(torch.bfloat16)
+        prev = torch.randint(0, VOCAB, (rows, 8), generator=gen, device="cuda")
+        bs = torch.zeros(rows, device="cuda") if order else None
+        x = (torch.randn(1, 320, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        eng = CachedDecoder(net)
+        eng.reserve(rows, 2 * args.repeats + 16)
+        eng.prefill(x, torch.ones(1, 320, dtype=torch.int64, device="cuda"))
+        eng.expand(rows)
+        tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+        select = lambda: eng.select(lg, prev, 3.0, 1, 2, bs, order, k)                                    # noqa: E731
+        cell = {"rows": rows, "k": k, "order": order, "select": timed(select, args.repeats), "sample": {}}
+        for name, (temperature, top_k, top_p) in {"top_k50_top_p0.9": (1.0, 50, 0.9), "top_p0.9": (0.7, 0, 0.9),
+                                                  "top_k50": (1.0, 50, 1.0), "no_warper": (1.0, 0, 1.0)}.items():
+            draw = lambda: eng.sample(lg, prev, 3.0, 1, 2, bs, order, temperature, top_k, top_p, 1 + order, k, 1, 0, 0)  # noqa: E731,B023
+            cell["sample"][name] = timed(draw, args.repeats)
+        cell["step_then_select"] = timed(lambda: (eng.step(tok), select()), args.repeats)
+        cell["step_then_sample"] = timed(lambda: (eng.step(tok), eng.sample(lg, prev, 3.0, 1, 2, bs, order, 1.0, 50, 0.9,
+                                                                            1 + order, k, 1, 0, 0)), args.repeats)
+        out["cells"].append(cell)
+        del eng
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sample", action="store_true", help="time the draw kernel beside the select kernel and a step")
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--rows", default="1,5,20,32,40,64")
@@ -67,6 +102,8 @@ def main():
     ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
+    if args.sample:
+        return sample_cells(args)
     net = build(args.layers)
     emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
     gen = torch.Generator(device="cuda").manual_seed(1)
