@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 36
+#define MSR3D_ABI_VERSION 37
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -445,6 +445,42 @@ int msr3d_project_scatter_bf16(int B, int T, int n_scene, int E, int K, const lo
                                const float *bias, const unsigned char *scene_mask, int out_dtype,
                                void *inputs_embeds, long long *attention_mask, int *map_ws,
                                int *count_out, msr3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Image tokens (the reference's model/msr3d/msr3d.py:98-100 `llm_proj_img`, :233-252): the pooled
+ * feature of every real image is projected and written over the embedding of one image placeholder,
+ * before the scene tokens go in.  No host sync: a one-block kernel builds dest[k] = flat (b*T + t)
+ * position of the k-th placeholder (input_ids == img_token, row-major) and src[k] = flat slot of the
+ * k-th source -- mode 0 ("interleaved"): the k-th slot whose img_masks byte is set; mode 1 ("single"):
+ * slot k itself -- and leaves counts[0] = placeholders found, counts[1] = sources.  A second kernel
+ * writes, for k < n = min(counts[0], counts[1], B*N),
+ *     inputs_embeds[dest[k], :] = cast(bias + weight . img_fts[src[k], :])
+ * and, in mode 1, attention_mask[dest[k]] = img_masks[src[k]] (mode 0 leaves attention_mask alone).
+ * img_fts (B*N, C) f32, img_masks (B*N) bytes, weight (E, C) / bias (E, may be NULL) f32
+ * (weight_dtype must be 0 = f32), inputs_embeds (B*T, E) of out_dtype 0 = f32, 1 = f16, 2 = bf16,
+ * attention_mask (B, T) int64 (may be NULL).  The product runs on f32-input MFMA (fp32-class, the
+ * reference's Linear runs outside autocast), K ascending; bands of 64 compacted rows x slabs of 128
+ * columns, the grid sized by B*N, workgroups at or beyond n return at once.  dest, src: B*N ints each;
+ * counts: 2 ints.  C % 32 == 0, E % 128 == 0, 16-byte aligned pointers, B*T and B*N below 2^31;
+ * MSR3D_EINVAL otherwise. */
+int msr3d_image_project_scatter(int B, int T, int N, int C, int E, int mode, const long long *input_ids,
+                                long long img_token, const float *img_fts, const unsigned char *img_masks,
+                                const void *weight, int weight_dtype, const float *bias, int out_dtype,
+                                void *inputs_embeds, long long *attention_mask, int *dest, int *src,
+                                int *counts, msr3d_stream_t stream);
+
+/* Its backward, through the map of the forward call (cap = B*N entries of dest / src, counts as left
+ * there; BT = rows of d_inputs_embeds): with G[k, :] = d_inputs_embeds[dest[k], :] read in its stored
+ * dtype (g_dtype as out_dtype above) and n as above,
+ *     dW[e, c] (+)= sum_k G[k, e] img_fts[src[k], c]      db[e] (+)= sum_k G[k, e]      k ascending,
+ * accumulate = 1 adds into dW (E, C) / db (E, may be NULL), 0 stores (zeros when n == 0; accumulate = 1
+ * with n == 0 writes nothing).  A workgroup owns a 64 x 32 tile of dW and walks all n rows in order: no
+ * partial sums, no workspace, no atomics.  clear_rows = 1 then sets rows dest[k], k < n, of
+ * d_inputs_embeds to zero (the overwritten embeddings receive no gradient).  Same domain as the
+ * forward; MSR3D_EINVAL otherwise. */
+int msr3d_image_project_grad(int cap, int C, int E, int BT, const int *dest, const int *src,
+                             const int *counts, const float *img_fts, int g_dtype, void *d_inputs_embeds,
+                             float *dW, float *db, int accumulate, int clear_rows, msr3d_stream_t stream);
 
 /* CUs the persistent set-abstraction kernels (msr3d_sa_level_split levels 1 and 2) leave to OTHER kernels:
  * their grids are sized to the chip, so a kernel that holds CUs beside them -- RCCL's gradient all-reduce,

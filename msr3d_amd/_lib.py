@@ -246,6 +246,9 @@ _SIGNATURES = {
                             _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_project_scatter_bf16": [_c_int, _c_int, _c_int, _c_int, _c_int, _ptr, ctypes.c_longlong, _ptr, _ptr,
                                    _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "msr3d_image_project_scatter": [_c_int] * 6 + [_ptr, ctypes.c_longlong, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int,
+                                    _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "msr3d_image_project_grad": [_c_int] * 4 + [_ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr],
     "msr3d_set_reserved_cus": [_c_int],
     "msr3d_dot_f32": [ctypes.c_longlong, _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_adamw_flat": [ctypes.c_longlong, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_float, _c_float,
@@ -276,7 +279,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 36       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 37       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def load():

@@ -37,6 +37,7 @@ SOURCES = [
     ("rowops.hip", []),
     ("prologue.hip", ["-ffp-contract=off"]),
     ("scene_scatter.hip", []),
+    ("image_tokens.hip", []),
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("bn_train.hip", []),
     ("strip_gemm.hip", []),

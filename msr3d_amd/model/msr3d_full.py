@@ -5,17 +5,22 @@
 
     scene dict ─► MSR3DHotPath (visual_prompter + llm_proj)                 ─► scene_embeds (B, L, E) fp32
     input_ids | output_ids ─► embed_tokens (frozen, bf16)                     ─► inputs_embeds (B, T, E) bf16
+                 project_scatter_images_train_ (optional: `image_tokens`)     ─► inputs_embeds (image placeholder rows)
                  scatter_scene_embeds_train_ (placeholder rows, mask rows)    ─► inputs_embeds, attention_mask
                  LoRALlamaStack (n decoder layers + norm + head) + seq-CE     ─► loss (B,)
 
 What is NOT here (out of SURVEY §8's scope): tokenizer and prompt assembly (the step takes
-token ids), the 2D image branch (`image_encoder`, `llm_proj_img`: one placeholder token per sequence), CLIP fusion, and of the reference's `generate`
-only `pred_action`.
+token ids), the frozen 2D image backbone (`image_encoder`: ConvNeXt under no_grad, its pooled output is cacheable and comes in as
+`img_fts`), CLIP fusion, and of the reference's `generate` only `pred_action`.
+The 2D image branch from the backbone's pooled output on (msr3d.py:98-100 `llm_proj_img`, :233-252) is opt-in through
+`cfg.image_tokens` (msr3d_amd/model/image_tokens.py): the projected feature of every real image replaces the embedding of one
+image placeholder before the scene tokens go in, in training, `generate` and `predict_answers` alike.
 `MSR3DFullStep.generate` is the reference's evaluation path (msr3d.py:445-524): prompt embeddings + scene tokens + one bos
 embedding -> KV-cached greedy / beam search, nucleus sampling or beam sampling, `num_captions` results per prompt
 (msr3d_amd/llm/generate.py) -> `output_tokens`.  `MSR3DFullStep.predict_answers` is
 its closed-vocabulary path (msr3d.py:526-655): the same prompt, prefilled once, and the candidate answers scored as
-short suffixes on that one cache (`rank_answers`) -> `answers_id`.  Parameter names: `visual_prompter.*` and `llm_proj.*` as in the reference's MSR3D; the language model
+short suffixes on that one cache (`rank_answers`) -> `answers_id`.  Parameter names: `visual_prompter.*`, `llm_proj.*` and
+`llm_proj_img.*` as in the reference's MSR3D (a reference `pytorch_model.bin` loads them with no mapping); the language model
 under `llm_model.*` (msr3d_amd/llm/checkpoint.py maps Hugging Face / peft keys onto it).
 
 GPU only beyond the prompter: the language-model kernels have no CPU fallback."""
@@ -23,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from .build import MODEL_REGISTRY
+from .image_tokens import IMG_SP_TOKEN, MODES, project_scatter_images_, project_scatter_images_train_
 from .scene_embeds import SCENE_SP_TOKEN, MSR3DHotPath, scatter_scene_embeds_, scatter_scene_embeds_train_
 
 
@@ -40,7 +46,10 @@ def build_targets(T_in, output_ids, output_mask):
 class MSR3DFullStep(MSR3DHotPath):
     """cfg: `prompter`, `llm_hidden_size` as MSR3DHotPath, plus `llm`: {num_layers, hidden_size, num_heads,
     intermediate_size, vocab_size, lora: {rank, alpha}, rms_eps, rope_theta, base: 'bf16' | 'fp8'}, optional `scene_sp_token` and `device`
-    (the language model's weights -- 26 GB in both orientations for Vicuna-7B -- are created there directly)."""
+    (the language model's weights -- 26 GB in both orientations for Vicuna-7B -- are created there directly).
+    Optional `image_tokens`: {in_features: 1024, img_sp_token: 30861, image_mode: "interleaved" | "single"} adds the trainable
+    `llm_proj_img` (nn.Linear(in_features, hidden)) and the image write for batches that carry `img_fts (B, N, in_features)` /
+    `img_masks (B, N)`; without the block the model has no such parameter and nothing changes."""
 
     def __init__(self, cfg):
         super().__init__(cfg)
@@ -50,6 +59,21 @@ class MSR3DFullStep(MSR3DHotPath):
             raise ValueError("llm.hidden_size must equal llm_hidden_size (llm_proj's output width)")
         lora = llm.get("lora", {}) if hasattr(llm, "get") else {}
         dev = cfg.get("device", None) if hasattr(cfg, "get") else None
+        img = cfg.get("image_tokens", None) if hasattr(cfg, "get") else None
+        self.image_tokens = img is not None
+        if self.image_tokens:
+            # registered after llm_proj and before llm_model: reversed registration order stays the order backward produces
+            # gradients (LoRA pairs, llm_proj_img, llm_proj, the prompter)
+            self.img_sp_token = int(img.get("img_sp_token", IMG_SP_TOKEN))
+            self.image_mode = str(img.get("image_mode", "interleaved"))
+            if self.image_mode not in MODES:
+                raise ValueError(f"image_tokens.image_mode must be one of {sorted(MODES)}")
+            scene_tok = int(cfg.get("scene_sp_token", SCENE_SP_TOKEN))
+            if not 0 <= self.img_sp_token < int(llm.vocab_size):
+                raise ValueError("img_sp_token outside the vocabulary")
+            if self.img_sp_token == scene_tok:
+                raise ValueError("img_sp_token must differ from scene_sp_token")
+            self.llm_proj_img = torch.nn.Linear(int(img.get("in_features", 1024)), int(llm.hidden_size))
         self.llm_model = LoRALlamaStack(int(llm.num_layers), int(llm.hidden_size), int(llm.num_heads),
                                         int(llm.intermediate_size), int(llm.vocab_size),
                                         r=int(lora.get("rank", 16)), lora_alpha=int(lora.get("alpha", 16)),
@@ -63,9 +87,28 @@ class MSR3DFullStep(MSR3DHotPath):
             raise ValueError("scene_sp_token outside the vocabulary")
 
     def get_opt_params(self):
-        """Registration order = prompter, llm_proj, LoRA pairs layer 0..n-1: reversed by the gradient engine it is
-        the order backward produces them (last decoder layer first, the prompter last)."""
+        """Registration order = prompter, llm_proj, (llm_proj_img,) LoRA pairs layer 0..n-1: reversed by the gradient engine
+        it is the order backward produces them (last decoder layer first, the prompter last)."""
         return [p for p in self.parameters() if p.requires_grad]
+
+    def _write_images(self, emb, am, ids, data_dict, train):
+        """msr3d.py:233-252, before the scene tokens: only when the block is configured; a batch without `img_fts` writes
+        nothing.  train: through the autograd node, which is applied even then (n = 0, interleaved mode over one empty slot
+        per row) so that llm_proj_img receives its -- zero -- gradient in every step."""
+        if not self.image_tokens:
+            return emb
+        fts, msk, mode = data_dict.get("img_fts"), data_dict.get("img_masks"), self.image_mode
+        if fts is None:
+            if not (train and torch.is_grad_enabled()):
+                return emb
+            fts = emb.new_zeros((ids.shape[0], 1, self.llm_proj_img.in_features), dtype=torch.float32)
+            msk, mode = torch.zeros((ids.shape[0], 1), dtype=torch.bool, device=ids.device), "interleaved"
+        elif msk is None:
+            raise KeyError("img_fts without img_masks")
+        if train:
+            return project_scatter_images_train_(emb, am, ids, fts, msk, self.llm_proj_img, self.img_sp_token, mode)
+        project_scatter_images_(emb, am, ids, fts, msk, self.llm_proj_img, self.img_sp_token, mode)
+        return emb
 
     def embed_inputs(self, data_dict, scene_embeds, scene_mask):
         """-> inputs_embeds (B, T, E) bf16 with the scene tokens written in, attention_mask (B, T) int64 with the
@@ -77,6 +120,7 @@ class MSR3DFullStep(MSR3DHotPath):
         if ids.shape[1] % 64:
             raise ValueError("prompt + answer length must be a multiple of 64 tokens (left-pad the prompt)")
         emb = F.embedding(ids, self.embed_tokens)                         # (B, T, E) bf16, frozen table
+        emb = self._write_images(emb, am, ids, data_dict, train=True)
         emb = scatter_scene_embeds_train_(emb, am, ids, scene_embeds, scene_mask, self.scene_sp_token)
         return emb, am, build_targets(ids_in.shape[1], ids_out, am_out)
 
@@ -125,6 +169,7 @@ class MSR3DFullStep(MSR3DHotPath):
         ids = data_dict["input_ids"].contiguous()
         am = data_dict["attention_mask"].to(torch.int64).contiguous().clone()
         emb = F.embedding(ids, self.embed_tokens).contiguous()
+        self._write_images(emb, am, ids, data_dict, train=False)
         scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
         out = self.llm_model.generate(emb, am, self.embed_tokens, bos_id=bos_id, eos_id=eos_id, pad_id=eos_id,
                                       num_beams=num_beams, max_length=max_length, min_length=min_length,
@@ -158,6 +203,7 @@ class MSR3DFullStep(MSR3DHotPath):
         ids = data_dict["input_ids"].contiguous()
         am = data_dict["attention_mask"].to(torch.int64).contiguous().clone()
         emb = F.embedding(ids, self.embed_tokens).contiguous()
+        self._write_images(emb, am, ids, data_dict, train=False)
         scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
         out = self.llm_model.predict_answers(emb, am, self.embed_tokens, answer_ids, answer_mask,
                                              num_ans_candidates=num_ans_candidates, bos_id=bos_id)

@@ -112,3 +112,36 @@ def synth_text(seed, B, L=60, T_in=544, T_out=32, vocab=32000, scene_token=31495
         om[b, :n_ans] = 1
     return {"input_ids": torch.from_numpy(ids).to(device), "attention_mask": torch.from_numpy(am).to(device),
             "output_ids": torch.from_numpy(out).to(device), "output_mask": torch.from_numpy(om).to(device)}
+
+
+def synth_images(seed, text, N, C, img_token, counts=None, mode="interleaved", scene_token=31495, bos_id=1):
+    """Image side of a synthetic MSQA sample (msr3d.py:233-252), on top of `text` (synth_text's dict, not modified):
+    `counts[b]` real prompt tokens of row b become `img_token` -- never a scene placeholder, bos or padding, and any
+    random word that happened to equal `img_token` is replaced first, so a row holds exactly counts[b] placeholders --
+    and img_fts (B, N, C) f32 ~ N(0, 1) stand for the backbone's pooled output, img_masks (B, N) bool set on the first
+    counts[b] slots.  counts: per-row list (default: U{0..N} per row; mode "single": N = 1 and one placeholder per row
+    whatever the mask says, counts then only sets the mask).  -> dict with input_ids, img_fts, img_masks on text's device."""
+    rng = np.random.default_rng(seed)
+    dev = text["input_ids"].device
+    ids = text["input_ids"].cpu().numpy().copy()
+    am = text["attention_mask"].cpu().numpy()
+    B = ids.shape[0]
+    if mode == "single" and N != 1:
+        raise ValueError('mode "single" has one image slot per row')
+    if counts is None:
+        counts = [int(rng.integers(0, N + 1)) for _ in range(B)]
+    if len(counts) != B or any(not 0 <= c <= N for c in counts):
+        raise ValueError("counts: one value in 0..N per row")
+    ids[ids == img_token] = 3
+    for b in range(B):
+        free = np.flatnonzero((am[b] != 0) & (ids[b] != scene_token) & (ids[b] != bos_id))
+        k = 1 if mode == "single" else counts[b]
+        if k > free.size:
+            raise ValueError(f"row {b} has {free.size} free prompt tokens for {k} image placeholders")
+        ids[b, np.sort(rng.choice(free, k, replace=False))] = img_token
+    fts = rng.standard_normal((B, N, C)).astype(np.float32)
+    masks = np.zeros((B, N), bool)
+    for b in range(B):
+        masks[b, :counts[b]] = True
+    return {"input_ids": torch.from_numpy(ids).to(dev), "img_fts": torch.from_numpy(fts).to(dev),
+            "img_masks": torch.from_numpy(masks).to(dev)}
