@@ -390,7 +390,7 @@ _BF16_ENTRIES = ("msr3d_scene_block", "msr3d_wgrad_split", "msr3d_wgrad_split_co
 
 
 def load_bf16():
-    """libmsr3d_hip_bf16.so: csrc/scene_block.hip + csrc/wgrad_split.hip compiled with MSR3D_TRAIN_PLANES=1 -- the
+    """libmsr3d_hip_bf16.so: csrc/scene_block.hip + csrc/wgrad_split.hip compiled with MSR3D_SPLIT_TERMS=1 -- the
     LABELLED reduced variant MSR3D_TRAIN_MMA=bf16 / scene_blocks.set_train_mma("bf16") of the trainable part: one bf16
     MFMA product of bf16-rounded operands per product instead of six, fp32 accumulate.  Same entry names, signatures and
     buffer layouts as the main library's; loaded only on request."""

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libmsr3d_hip.so")
 # compiled with MSR3D_SPLIT_TERMS=3, under the same entry names
 LIB_SPLIT2 = os.path.join(HERE, "libmsr3d_hip_split2.so")
 # the labelled bf16 variant of the trainable part (MSR3D_TRAIN_MMA=bf16): csrc/scene_block.hip + csrc/wgrad_split.hip
-# compiled with MSR3D_TRAIN_PLANES=1 (one bf16 MFMA product per product instead of six), under the same entry names
+# compiled with MSR3D_SPLIT_TERMS=1 (one bf16 MFMA product per product instead of six), under the same entry names
 LIB_BF16 = os.path.join(HERE, "libmsr3d_hip_bf16.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
@@ -115,7 +115,7 @@ def build(force=False, verbose=False, sqdist_contract=None):
         subprocess.check_call(cmd)
     srcs = [os.path.join(CSRC, "scene_block.hip"), os.path.join(CSRC, "wgrad_split.hip")]
     if force or not os.path.exists(LIB_BF16) or os.path.getmtime(LIB_BF16) < max([os.path.getmtime(x) for x in srcs] + [hdr_t]):
-        cmd = [cc] + COMMON + ["-DMSR3D_TRAIN_PLANES=1", "-shared"] + srcs + ["-o", LIB_BF16]
+        cmd = [cc] + COMMON + ["-DMSR3D_SPLIT_TERMS=1", "-shared"] + srcs + ["-o", LIB_BF16]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

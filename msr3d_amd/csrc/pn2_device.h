@@ -641,6 +641,29 @@ __global__ __launch_bounds__(kWave * NW) void ball_query_kernel(int n, int m, fl
   }
 }
 
+// Ball query of ONE centre by ONE wave over a cloud staged in LDS (packed xyz), result in an LDS row of
+// `nsample` ints: what the fused set-abstraction kernels (sa_fused.hip, sa_split.hip) run per centre.  Same
+// semantics as ball_query_kernel: index order, strict '<', first-hit fill, zeros when empty.
+__device__ __forceinline__ void wave_ball_query(const float *sx, int n, float cx, float cy, float cz,
+                                                float radius2, int nsample, int *row, int lane) {
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  int cnt = 0, first = 0;
+  for (int base = 0; base < n && cnt < nsample; base += kWave) {
+    const int k = base + lane;
+    bool hit = false;
+    if (k < n) hit = sq3(cx - sx[k * 3 + 0], cy - sx[k * 3 + 1], cz - sx[k * 3 + 2]) < radius2;
+    const unsigned long long mask = __ballot(hit);
+    if (mask) {
+      if (cnt == 0) first = base + __ffsll((long long)mask) - 1;
+      const int slot = cnt + __popcll(mask & lt);
+      if (hit && slot < nsample) row[slot] = k;
+      cnt += __popcll(mask);
+    }
+  }
+  const int filled = cnt < nsample ? cnt : nsample;
+  const int fill = cnt > 0 ? first : 0;
+  for (int l = filled + lane; l < nsample; l += kWave) row[l] = fill;
+}
 
 inline hipError_t launch_ball_query(int b, int n, int ps, int m, float radius2, int nsample,
                                     const float *new_xyz, const float *xyz, int *idx,

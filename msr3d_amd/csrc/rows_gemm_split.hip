@@ -188,16 +188,11 @@ __global__ __launch_bounds__(512, 1) void rows_gemm_split_kernel(const RowsGemm 
           bf16x8 fb[3];
 #pragma unroll
           for (int q = 0; q < 3; ++q) fb[q] = *reinterpret_cast<const bf16x8 *>(bl + ((s * NT + t) * 3 + q) * 1024);
-#define MSR3D_TERM(PB, PA)                                                                            \
+#define MSR3D_MMA(PB, PA)                                                                             \
           _Pragma("unroll") for (int rt = 0; rt < 2; ++rt)                                            \
               acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[PB], fa[rt][PA], acc[rt][t], 0, 0, 0);
-          MSR3D_TERM(2, 0)
-          MSR3D_TERM(0, 2)
-          MSR3D_TERM(1, 1)
-          MSR3D_TERM(1, 0)
-          MSR3D_TERM(0, 1)
-          MSR3D_TERM(0, 0)
-#undef MSR3D_TERM
+          MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
         }
       }
     }

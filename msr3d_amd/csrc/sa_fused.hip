@@ -258,35 +258,6 @@ struct Chain {
   }
 };
 
-// ---------------------------------------------------------------------------------
-// Ball query of ONE centre by ONE wave over a cloud staged in LDS (packed xyz), result in
-// an LDS row of `nsample` ints.  Same semantics as ball_query_kernel in pn2_ops.hip
-// (ball_query_gpu.cu:9-44): index order, strict '<', first-hit fill, zeros when empty.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_ball_query(const float *sx, int n, float cx, float cy, float cz,
-                                                float radius2, int nsample, int *row, int lane) {
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  int cnt = 0, first = 0;
-  for (int base = 0; base < n && cnt < nsample; base += kWave) {
-    const int k = base + lane;
-    bool hit = false;
-    if (k < n) {
-      const float d2 = sq3(cx - sx[k * 3 + 0], cy - sx[k * 3 + 1], cz - sx[k * 3 + 2]);
-      hit = d2 < radius2;
-    }
-    const unsigned long long mask = __ballot(hit);
-    if (mask) {
-      if (cnt == 0) first = base + __ffsll((long long)mask) - 1;
-      const int slot = cnt + __popcll(mask & lt);
-      if (hit && slot < nsample) row[slot] = k;
-      cnt += __popcll(mask);
-    }
-  }
-  const int filled = cnt < nsample ? cnt : nsample;
-  const int fill = cnt > 0 ? first : 0;
-  for (int l = filled + lane; l < nsample; l += kWave) row[l] = fill;
-}
-
 // =================================================================================
 // Level 1: points (b, n, 6) = [xyz, rgb] as the dataset stores them; centres (b, m, 3).
 // Block = CPB centres x 32 neighbours (default 2 -> 64 rows).  MLP 6 -> 64 -> 64 -> 128.  The ball

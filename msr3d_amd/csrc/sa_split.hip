@@ -48,23 +48,10 @@
 
 #include "../../include/msr3d_hip.h"
 #include "pn2_device.h"
+#include "split_mma.h"         // the split, the weight stream, the operand forms and the product; MSR3D_SPLIT_TERMS
 
 // phase marks of the level-2 kernel: empty here; tools/prof/sa_split_stamped.hip defines them and includes
 // this file (tools/ab_split.py reads the stamps)
-// MSR3D_SPLIT_TERMS = 3 (python -m msr3d_amd.build builds libmsr3d_hip_split2.so from this file with it): the LABELLED
-// reduced variant MSR3D_SA_MMA=split2 -- two bf16 terms per operand, the three products x0 w0 + x0 w1 + x1 w0 (~16
-// significant bits per product; the reference's cuDNN convolutions run TF32, 10 bits, by default on any Ampere-or-later
-// GPU: README.md:81 pins torch 1.12.1 and nothing in the reference touches allow_tf32).  Never the headline.
-#ifndef MSR3D_SPLIT_TERMS
-#define MSR3D_SPLIT_TERMS 6
-#endif
-#if MSR3D_SPLIT_TERMS == 6     // smallest first: the accumulator meets the big terms last
-#define MSR3D_TERMS_ALL MSR3D_TERM(2, 0) MSR3D_TERM(0, 2) MSR3D_TERM(1, 1) MSR3D_TERM(1, 0) MSR3D_TERM(0, 1) MSR3D_TERM(0, 0)
-#elif MSR3D_SPLIT_TERMS == 3
-#define MSR3D_TERMS_ALL MSR3D_TERM(1, 0) MSR3D_TERM(0, 1) MSR3D_TERM(0, 0)
-#else
-#error "MSR3D_SPLIT_TERMS must be 6 or 3"
-#endif
 #ifndef RSTAMP                 // phase marks of the distinct-row kernels (tools/prof/sa_rows_stamped.hip)
 #define RSTAMP(i)
 #define RSTAMP_DECL
@@ -78,11 +65,6 @@
 namespace {
 
 using namespace msr3d;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kNS = 32;           // neighbours per centre (configs/msr3d.yaml:199)
 constexpr int kFragS = 512;       // bf16 per (slab, tile, plane) block: 64 lanes x 8
 constexpr int kPadH = 16;         // LDS row stride = K + 16 bf16: conflict-free 16-byte fragment reads
@@ -91,111 +73,6 @@ struct LayerS {
   const unsigned short *w;        // [K/32][N/16][3][64][8] bf16, fragment order
   const float *scale, *shift;     // [N]
 };
-
-// ---- exact three-way split of fp32 values into bf16 (RNE) ------------------------------------------
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {       // v_cvt_pk_bf16_f32
-  const f32x2 v = {a, b};
-  const bf16x2 r = __builtin_convertvector(v, bf16x2);
-  return *reinterpret_cast<const unsigned *>(&r);
-}
-// four values -> three planes of four bf16 (8 bytes each)
-__device__ __forceinline__ void split4(const float (&v)[4], uint2 (&p)[3]) {
-  float a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const unsigned lo = pk_bf16(a0, a1), hi = pk_bf16(a2, a3);
-    p[k] = make_uint2(lo, hi);
-    if (k < 2) {
-      a0 -= __uint_as_float(lo << 16); a1 -= __uint_as_float(lo & 0xffff0000u);
-      a2 -= __uint_as_float(hi << 16); a3 -= __uint_as_float(hi & 0xffff0000u);
-    }
-  }
-}
-
-// One PIECE of weights = one (slab, column tile): three planes, 3 x 1 KB coalesced reads per wave.
-// Pieces are consumed in (slab, tile) order and fetched D pieces ahead through a register ring, so a
-// wave keeps D x 3 KB in flight whatever the layer width (tools/probe/l2_stream.hip: the L2 -> CU
-// stream needs >= 8 loads in flight per wave to pass 30 B/clk/CU).
-struct WPiece { bf16x8 v[3]; };
-
-// The stream goes through a buffer descriptor: wave-uniform base (SGPRs) + one per-lane byte offset +
-// an SGPR piece offset.  With flat loads hipcc materialises every piece's 64-bit address in its own
-// VGPR pair and hoists them all out of the persistent loop (~180 VGPRs, all spilled).
-struct WStream {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int voff;                        // lane * 16
-  int soff;                        // the wave's first column tile, bytes
-};
-template <int RN>
-__device__ __forceinline__ WStream make_stream(const unsigned short *w, int bytes, int wave_uniform, int lane) {
-  WStream st;
-  st.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(w), 0, bytes, 0x00020000);
-  st.voff = lane * 16;
-  st.soff = wave_uniform * RN * 3 * kFragS * 2;
-  return st;
-}
-
-template <int NT>
-__device__ __forceinline__ void load_piece(WPiece &f, const WStream &st, int s, int rn, int /*lane*/) {
-  const int piece = st.soff + (s * NT + rn) * 3 * kFragS * 2;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    const i32x4 r = __builtin_amdgcn_raw_buffer_load_b128(st.rsrc, st.voff, piece + p * kFragS * 2, 0);
-    f.v[p] = *reinterpret_cast<const bf16x8 *>(&r);
-  }
-}
-
-template <int RN, int NT, int D>
-__device__ __forceinline__ void preload_ring(WPiece (&ring)[D], const WStream &st, int lane) {
-#pragma unroll
-  for (int q = 0; q < D; ++q) load_piece<NT>(ring[q], st, q / RN, q % RN, lane);
-}
-
-// acc[rn][mt] (+)= W[n-tile rn] X[m-tile mt]^T over KS slabs of 32.  X: LDS planes [3][TM][ldh] bf16.
-// D layout: lane (j = lane & 15, g = lane >> 4) holds rows n = 4 g + r (r = 0..3), column m = j.
-// `ring` holds pieces 0..D-1 on entry (fetched under the previous phase).
-template <int RN, int MT, int KS, int NT, int D>
-__device__ __forceinline__ void gemm_split(const unsigned short *xs, int ldh, int plane, const WStream &wg,
-                                           f32x4 (&acc)[RN][MT], int lane, const WPiece (&ring)[D]) {
-  constexpr int NP = KS * RN;
-  static_assert(D <= NP, "ring deeper than the layer");
-  const int j = lane & 15, g = lane >> 4;
-  const unsigned short *xp = xs + j * ldh + 8 * g;
-  WPiece w[NP];                    // fully unrolled: only a window of D + 1 pieces is ever live
-#pragma unroll
-  for (int q = 0; q < D; ++q) w[q] = ring[q];
-  bf16x8 x[MT][3];                 // one slab of the operand (prefetching the next one a piece early: no gain)
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int s = q / RN, rn = q % RN;
-    __builtin_amdgcn_sched_barrier(0);          // this piece's fetches stay below the previous piece's MFMAs ..
-    if (q + D < NP) load_piece<NT>(w[q + D], wg, (q + D) / RN, (q + D) % RN, lane);
-    if (rn == 0) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-          x[mt][p] = *reinterpret_cast<const bf16x8 *>(xp + p * plane + mt * 16 * ldh + 32 * s);
-    }
-    __builtin_amdgcn_sched_barrier(0);          // .. and above its own
-    // the six significant products, SMALLEST first (the accumulator meets the big terms last);
-    // consecutive MFMAs hit different accumulators
-#define MSR3D_TERM(PW, PX)                                                                             \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                  \
-        acc[rn][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[q].v[PW], x[mt][PX], acc[rn][mt], 0, 0, 0);
-    MSR3D_TERMS_ALL
-#undef MSR3D_TERM
-  }
-}
-
-template <int RN, int MT>
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[RN][MT]) {
-#pragma unroll
-  for (int a = 0; a < RN; ++a)
-#pragma unroll
-    for (int b = 0; b < MT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
 
 // y = relu(acc * scale[n] + shift[n]), split, -> LDS planes [3][TM][ldy] at columns n0 + 16 rn + 4 g ..
 template <int RN, int MT>
@@ -212,7 +89,7 @@ __device__ __forceinline__ void store_split(const f32x4 (&acc)[RN][MT], const fl
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = fmaxf(__builtin_fmaf(acc[rn][mt][r], s4[r], h4[r]), 0.0f);
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
       unsigned short *d = ys + (mt * 16 + j) * ldy + n0 + rn * 16 + 4 * g;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * plane) = p[k];
@@ -220,7 +97,7 @@ __device__ __forceinline__ void store_split(const f32x4 (&acc)[RN][MT], const fl
   }
 }
 
-// ---- level 2 (round 3): operand planes in two layouts ------------------------------------------------------
+// ---- level 2 (round 3): operand planes in two layouts (split_mma.h's XRows and XFrag<4>) -------------------
 // ROWS  [3][rows][pitch] row-major: what the gather writes (16 lanes per row, 8 contiguous bytes each: one
 //       bank row per store group); pitch = K + 16 bf16 keeps the 16-byte fragment reads conflict-free.
 // FRAG  [slab][4 row tiles][3 planes][64 lanes][16 B] MFMA-fragment order: what an epilogue writes.  A lane
@@ -228,49 +105,6 @@ __device__ __forceinline__ void store_split(const f32x4 (&acc)[RN][MT], const fl
 //       (row, channel / 8); the 16 lanes of a store group are 16 rows = 16 consecutive 16-byte slots: two
 //       lanes per bank row instead of the four the row-major image gave (38 % of this kernel's LDS cycles
 //       were those conflicts, profiles/r02_v6_pmc_sa.txt), and every fragment READ is a contiguous 1 KB.
-struct XRowsS {
-  const unsigned short *base;      // + j * pitch + 8 g
-  int pitch, plane;
-  __device__ __forceinline__ bf16x8 operator()(int mt, int s, int p) const {
-    return *reinterpret_cast<const bf16x8 *>(base + p * plane + mt * 16 * pitch + 32 * s);
-  }
-};
-struct XFragS {
-  const unsigned short *base;      // + lane * 8
-  __device__ __forceinline__ bf16x8 operator()(int mt, int s, int p) const {
-    return *reinterpret_cast<const bf16x8 *>(base + ((s * 4 + mt) * 3 + p) * 512);
-  }
-};
-
-template <int RN, int MT, int KS, int NT, int D, typename XF>
-__device__ __forceinline__ void gemm_split_x(const XF &xf, const WStream &wg, f32x4 (&acc)[RN][MT], int lane,
-                                             const WPiece (&ring)[D]) {
-  constexpr int NP = KS * RN;
-  static_assert(D <= NP, "ring deeper than the layer");
-  WPiece w[NP];
-#pragma unroll
-  for (int q = 0; q < D; ++q) w[q] = ring[q];
-  bf16x8 x[MT][3];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int s = q / RN, rn = q % RN;
-    __builtin_amdgcn_sched_barrier(0);
-    if (q + D < NP) load_piece<NT>(w[q + D], wg, (q + D) / RN, (q + D) % RN, lane);
-    if (rn == 0) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) x[mt][p] = xf(mt, s, p);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#define MSR3D_TERM(PW, PX)                                                                             \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                  \
-        acc[rn][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[q].v[PW], x[mt][PX], acc[rn][mt], 0, 0, 0);
-    MSR3D_TERMS_ALL
-#undef MSR3D_TERM
-  }
-}
-
 // y = relu(acc * scale[n] + shift[n]), split -> FRAG planes (4 row tiles) at channels n0 + 16 rn + 4 g ..
 template <int RN, int MT>
 __device__ __forceinline__ void store_split_frag(const f32x4 (&acc)[RN][MT], const float4 (&sc)[RN], const float4 (&sh)[RN],
@@ -280,17 +114,17 @@ __device__ __forceinline__ void store_split_frag(const f32x4 (&acc)[RN][MT], con
   for (int rn = 0; rn < RN; ++rn) {
     const float s4[4] = {sc[rn].x, sc[rn].y, sc[rn].z, sc[rn].w};
     const float h4[4] = {sh[rn].x, sh[rn].y, sh[rn].z, sh[rn].w};
-    const int c = n0 + rn * 16 + 4 * g, slab = c >> 5, kk = c & 31;
+    const int c = n0 + rn * 16 + 4 * g;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = fmaxf(__builtin_fmaf(acc[rn][mt][r], s4[r], h4[r]), 0.0f);
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
 #pragma unroll
       for (int k = 0; k < 3; ++k)
-        *reinterpret_cast<uint2 *>(ys + ((((slab * 4 + mt) * 3 + k) * 64 + j + 16 * (kk >> 3)) * 16 + (kk & 7) * 2)) = p[k];
+        *reinterpret_cast<uint2 *>(ys + frag_off4<4>(mt, j, c, k)) = p[k];
     }
   }
 }
@@ -367,29 +201,6 @@ __device__ __forceinline__ void load_affine4(const float *__restrict__ scale, co
     sc[rn] = *reinterpret_cast<const float4 *>(scale + n0 + rn * 16 + 4 * g);
     sh[rn] = *reinterpret_cast<const float4 *>(shift + n0 + rn * 16 + 4 * g);
   }
-}
-
-// ball query of ONE centre by ONE wave over a cloud staged in LDS (sa_fused.hip's, verbatim semantics:
-// ball_query_gpu.cu:9-44 -- index order, strict '<', first-hit fill, zeros when empty)
-__device__ __forceinline__ void wave_ball_query(const float *sx, int n, float cx, float cy, float cz, float radius2,
-                                                int nsample, int *row, int lane) {
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  int cnt = 0, first = 0;
-  for (int base = 0; base < n && cnt < nsample; base += kWave) {
-    const int k = base + lane;
-    bool hit = false;
-    if (k < n) hit = sq3(cx - sx[k * 3 + 0], cy - sx[k * 3 + 1], cz - sx[k * 3 + 2]) < radius2;
-    const unsigned long long mask = __ballot(hit);
-    if (mask) {
-      if (cnt == 0) first = base + __ffsll((long long)mask) - 1;
-      const int slot = cnt + __popcll(mask & lt);
-      if (hit && slot < nsample) row[slot] = k;
-      cnt += __popcll(mask);
-    }
-  }
-  const int filled = cnt < nsample ? cnt : nsample;
-  const int fill = cnt > 0 ? first : 0;
-  for (int l = filled + lane; l < nsample; l += kWave) row[l] = fill;
 }
 
 // =====================================================================================================
@@ -485,10 +296,10 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
 
   constexpr int RN1 = kN1 / 64, RN2 = kN2 / 64, RN3 = kN3 / 64, MT = kTM / 16, GT = kNS / 16;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);                 // uniform to the compiler as well
-  const WStream w1 = make_stream<RN1>(l1.w, kK0 * kN1 * 6, wave_u, lane);
+  const WStream w1 = make_wstream(l1.w, kK0 * kN1 * 6, kN1 / 16, 0, wave_u * RN1, lane);
   const float *__restrict__ wxyz = l1.shift + kN1;                         // [128][4] fp32: layer 1's weights on (dx, dy, dz)
-  const WStream w2 = make_stream<RN2>(l2.w, kN1 * kN2 * 6, wave_u, lane);
-  const WStream w3 = make_stream<RN3>(l3.w, kN2 * kN3 * 6, wave_u, lane);
+  const WStream w2 = make_wstream(l2.w, kN1 * kN2 * 6, kN2 / 16, 0, wave_u * RN2, lane);
+  const WStream w3 = make_wstream(l3.w, kN2 * kN3 * 6, kN3 / 16, 0, wave_u * RN3, lane);
 
   // ---- the pieces of a tile's query + gather ----
   float geo = 0.f;                           // one xyz / centre coordinate of the NEXT tile per thread
@@ -532,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
       const int e = tid + it * 256;
       const float v[4] = {val[it].x, val[it].y, val[it].z, val[it].w};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
       unsigned short *d = buf + (e >> 5) * kLd + (e & 31) * 4;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * kPlane) = p[k];
@@ -546,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
 
   // ---- prologue: the first tile's operand, unpipelined ----
   WPiece ring1[kRing];
-  preload_ring<RN1, kN1 / 16, kRing>(ring1, w1, lane);
+  preload_wring<RN1, kRing, kN1 / 16>(ring1, w1);
   geo_fetch(T);
   geo_store();
   __syncthreads();
@@ -570,10 +381,10 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
     WPiece ring2[kRing], ring3[kRing];
     {
       f32x4 acc[RN1][MT];
-      zero_acc(acc);
-      const XRowsS x1{buf + (lane & 15) * kLd + 8 * (lane >> 4), kLd, kPlane};
-      gemm_split_x<RN1, MT, kK0 / 32, kN1 / 16, kRing>(x1, w1, acc, lane, ring1);
-      preload_ring<RN2, kN2 / 16, kRing>(ring2, w2, lane);        // the next layer's operands fly under the epilogue
+      zero_acc3(acc);
+      const XRows x1{buf + (lane & 15) * kLd + 8 * (lane >> 4), kLd, kPlane};
+      gemm_split3<true, RN1, MT, kK0 / 32, kRing, kN1 / 16>(x1, 0, w1, acc, ring1);
+      preload_wring<RN2, kRing, kN2 / 16>(ring2, w2);        // the next layer's operands fly under the epilogue
       float4 sc[RN1], sh[RN1];
       load_affine4<RN1>(sc1, sh1, wave * RN1 * 16, lane, sc, sh);
       {   // + W_xyz (dx, dy, dz): lane (j, g) holds row 16 mt + j, channels n0 + 16 rn + 4 g + r
@@ -602,10 +413,10 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
     if (more) query(Tn);
     {
       f32x4 acc[RN2][MT];
-      zero_acc(acc);
-      const XFragS x2{buf + lane * 8};
-      gemm_split_x<RN2, MT, kN1 / 32, kN2 / 16, kRing>(x2, w2, acc, lane, ring2);
-      preload_ring<RN3, kN3 / 16, kRing>(ring3, w3, lane);
+      zero_acc3(acc);
+      const XFrag<4> x2{buf + lane * 8};
+      gemm_split3<true, RN2, MT, kN1 / 32, kRing, kN2 / 16>(x2, 0, w2, acc, ring2);
+      preload_wring<RN3, kRing, kN3 / 16>(ring3, w3);
       float4 sc[RN2], sh[RN2];
       load_affine4<RN2>(sc2, sh2, wave * RN2 * 16, lane, sc, sh);
       STAMP(3);
@@ -619,9 +430,9 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
     if (more) touch = feat[((size_t)(Tn / tpo) * n + nbr[tid >> 2]) * 128 + (tid & 3) * 32];   // towards this XCD's L2
     {
       f32x4 acc[RN3][MT];
-      zero_acc(acc);
-      const XFragS x3{buf + lane * 8};
-      gemm_split_x<RN3, MT, kN2 / 32, kN3 / 16, kRing>(x3, w3, acc, lane, ring3);
+      zero_acc3(acc);
+      const XFrag<4> x3{buf + lane * 8};
+      gemm_split3<true, RN3, MT, kN2 / 32, kRing, kN3 / 16>(x3, 0, w3, acc, ring3);
       STAMP(5);
       float4 sc[RN3], sh[RN3];
       load_affine4<RN3>(sc3, sh3, wave * RN3 * 16, lane, sc, sh);
@@ -630,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void sa2_split_kernel(int n, int m, int til
     // (touched lines: L2 hits) fly under the row maxima.  UNCONDITIONAL -- after the last tile it re-reads
     // that tile: a conditional assignment would make val / ring1 loop-carried and live across the GEMMs
     feat_fetch(more ? Tn : T);
-    preload_ring<RN1, kN1 / 16, kRing>(ring1, w1, lane);
+    preload_wring<RN1, kRing, kN1 / 16>(ring1, w1);
     {
       int groups = m - c0;
       groups = groups < 2 ? groups : 2;
@@ -912,10 +723,10 @@ __global__ __launch_bounds__(256, 2) void sa2_rows_kernel(int b, int n, int m, c
                            *__restrict__ sh2 = l2.shift, *__restrict__ sc3 = l3.scale, *__restrict__ sh3 = l3.shift;
   constexpr int RN1 = kN1 / 64, RN2 = kN2 / 64, RN3 = kN3 / 64;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const WStream w1 = make_stream<RN1>(l1.w, kK0 * kN1 * 6, wave_u, lane);
+  const WStream w1 = make_wstream(l1.w, kK0 * kN1 * 6, kN1 / 16, 0, wave_u * RN1, lane);
   const float *__restrict__ wxyz = l1.shift + kN1;                         // [128][4] fp32: layer 1's weights on (dx, dy, dz)
-  const WStream w2 = make_stream<RN2>(l2.w, kN1 * kN2 * 6, wave_u, lane);
-  const WStream w3 = make_stream<RN3>(l3.w, kN2 * kN3 * 6, wave_u, lane);
+  const WStream w2 = make_wstream(l2.w, kN1 * kN2 * 6, kN2 / 16, 0, wave_u * RN2, lane);
+  const WStream w3 = make_wstream(l3.w, kN2 * kN3 * 6, kN3 / 16, 0, wave_u * RN3, lane);
   for (int i = tid; i < m * kOutPitch; i += 256) outb[i] = 0u;
   int ui = 0, un = s_mine[1];
   if (s_mine[0] < 0) return;
@@ -960,7 +771,7 @@ __global__ __launch_bounds__(256, 2) void sa2_rows_kernel(int b, int n, int m, c
       const int e = tid + it * 256;
       const float v[4] = {val[it].x, val[it].y, val[it].z, val[it].w};
       uint2 q[3];
-      split4(v, q);
+      sm_split4(v, q);
       unsigned short *d = buf + (e >> 5) * kLd + (e & 31) * 4;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * kPlane) = q[k];
@@ -1004,13 +815,13 @@ __global__ __launch_bounds__(256, 2) void sa2_rows_kernel(int b, int n, int m, c
       asm volatile("" : "+v"(t_));
       const int lane = t_ & 63, wave = t_ >> 6;
       WPiece ring1[kRing], ring2[kRing], ring3[kRing];
-      preload_ring<RN1, kN1 / 16, kRing>(ring1, w1, lane);
+      preload_wring<RN1, kRing, kN1 / 16>(ring1, w1);
       {
         f32x4 acc[RN1][MT];
-        zero_acc(acc);
-        const XRowsS x1{buf + (lane & 15) * kLd + 8 * (lane >> 4), kLd, kPlane};
-        gemm_split_x<RN1, MT, kK0 / 32, kN1 / 16, kRing>(x1, w1, acc, lane, ring1);
-        preload_ring<RN2, kN2 / 16, kRing>(ring2, w2, lane);
+        zero_acc3(acc);
+        const XRows x1{buf + (lane & 15) * kLd + 8 * (lane >> 4), kLd, kPlane};
+        gemm_split3<true, RN1, MT, kK0 / 32, kRing, kN1 / 16>(x1, 0, w1, acc, ring1);
+        preload_wring<RN2, kRing, kN2 / 16>(ring2, w2);
         float4 sc[RN1], sh[RN1];
         load_affine4<RN1>(sc1, sh1, wave * RN1 * 16, lane, sc, sh);
         {   // + W_xyz (dx, dy, dz), exactly as sa2_split_kernel
@@ -1036,10 +847,10 @@ __global__ __launch_bounds__(256, 2) void sa2_rows_kernel(int b, int n, int m, c
       RSTAMP(7);
       {
         f32x4 acc[RN2][MT];
-        zero_acc(acc);
-        const XFragS x2{buf + lane * 8};
-        gemm_split_x<RN2, MT, kN1 / 32, kN2 / 16, kRing>(x2, w2, acc, lane, ring2);
-        preload_ring<RN3, kN3 / 16, kRing>(ring3, w3, lane);
+        zero_acc3(acc);
+        const XFrag<4> x2{buf + lane * 8};
+        gemm_split3<true, RN2, MT, kN1 / 32, kRing, kN2 / 16>(x2, 0, w2, acc, ring2);
+        preload_wring<RN3, kRing, kN3 / 16>(ring3, w3);
         float4 sc[RN2], sh[RN2];
         load_affine4<RN2>(sc2, sh2, wave * RN2 * 16, lane, sc, sh);
         RSTAMP(8);
@@ -1050,9 +861,9 @@ __global__ __launch_bounds__(256, 2) void sa2_rows_kernel(int b, int n, int m, c
       RSTAMP(9);
       {
         f32x4 acc[RN3][MT];
-        zero_acc(acc);
-        const XFragS x3{buf + lane * 8};
-        gemm_split_x<RN3, MT, kN2 / 32, kN3 / 16, kRing>(x3, w3, acc, lane, ring3);
+        zero_acc3(acc);
+        const XFrag<4> x3{buf + lane * 8};
+        gemm_split3<true, RN3, MT, kN2 / 32, kRing, kN3 / 16>(x3, 0, w3, acc, ring3);
         RSTAMP(10);
         float4 sc[RN3], sh[RN3];
         load_affine4<RN3>(sc3, sh3, wave * RN3 * 16, lane, sc, sh);
@@ -1182,21 +993,21 @@ __device__ __forceinline__ void gemm_split_rolled(const unsigned short *xs, int 
   WPiece wa[RN], wb[RN];
   auto fetch = [&](WPiece (&w)[RN], int s) {
 #pragma unroll
-    for (int rn = 0; rn < RN; ++rn) load_piece<NT>(w[rn], wg, ws0 + s, t0 + rn, lane);     // (ws0: the weights' first slab)
+    for (int rn = 0; rn < RN; ++rn) load_wpiece<NT>(w[rn], wg, ws0 + s, t0 + rn);     // (ws0: the weights' first slab)
   };
   auto mma = [&](const WPiece (&w)[RN], int s) {
     bf16x8 x[MT][3];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
+      for (int p = 0; p < kPlanes; ++p)
         x[mt][p] = *reinterpret_cast<const bf16x8 *>(xp + p * plane + mt * 16 * ldh + 32 * s);
-#define MSR3D_TERM(PW, PX)                                                                             \
+#define MSR3D_MMA(PW, PX)                                                                              \
     _Pragma("unroll") for (int rn = 0; rn < RN; ++rn)                                                  \
     _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                  \
         acc[rn][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[rn].v[PW], x[mt][PX], acc[rn][mt], 0, 0, 0);
-    MSR3D_TERMS_ALL
-#undef MSR3D_TERM
+    MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
   };
   fetch(wa, 0);
 #pragma clang loop unroll(disable)      // (unrolled -- it is, at three row tiles -- every slab's pieces are hoisted: 3.8 KB of scratch a lane)
@@ -1226,9 +1037,9 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
   for (int i = tid; i < k3N2; i += 256) { aff[2 * k3N1 + i] = l2.scale[i]; aff[2 * k3N1 + k3N2 + i] = l2.shift[i]; }
   for (int i = tid; i < k3N3; i += 256) { aff[2 * (k3N1 + k3N2) + i] = l3.scale[i]; aff[2 * (k3N1 + k3N2) + k3N3 + i] = l3.shift[i]; }
   const float *sc1 = aff, *sh1 = aff + k3N1, *sc2 = aff + 2 * k3N1, *sh2 = sc2 + k3N2, *sc3 = aff + 2 * (k3N1 + k3N2), *sh3 = sc3 + k3N3;
-  const WStream w1 = make_stream<0>(l1.w, k3K0 * k3N1 * 6, 0, lane);
-  const WStream w2 = make_stream<0>(l2.w, k3N1 * k3N2 * 6, 0, lane);
-  const WStream w3 = make_stream<0>(l3.w, k3N2 * k3N3 * 6, 0, lane);
+  const WStream w1 = make_wstream(l1.w, k3K0 * k3N1 * 6, k3N1 / 16, 0, 0, lane);
+  const WStream w2 = make_wstream(l2.w, k3N1 * k3N2 * 6, k3N2 / 16, 0, 0, lane);
+  const WStream w3 = make_wstream(l3.w, k3N2 * k3N3 * 6, k3N3 / 16, 0, 0, lane);
   {   // operand: 32 rows x [feat(256), x, y, z, 0 ...]; all loads first, then split + LDS stores
     constexpr int IT = k3TM * 64 / 256;
     float4 val[IT];
@@ -1251,7 +1062,7 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
       const int e = tid + it * 256;
       const float v[4] = {val[it].x, val[it].y, val[it].z, val[it].w};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
       unsigned short *d = buf + (e >> 6) * k3Ld + (e & 63) * 4;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * k3Plane) = p[k];
@@ -1259,7 +1070,7 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
     if (tid < k3TM) {
       const float v[4] = {px, py, pz, 0.f};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         unsigned short *d = buf + k * k3Plane + tid * k3Ld + 256;
@@ -1274,7 +1085,7 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
   {
     constexpr int RN = k3N1 / 64;
     f32x4 acc[RN][MT];
-    zero_acc(acc);
+    zero_acc3(acc);
     gemm_split_rolled<RN, MT, k3N1 / 16>(buf, k3Ld, k3Plane, w1, wave_u * RN, k3K0 / 32, acc, lane);
     float4 sc[RN], sh[RN];
     load_affine4<RN>(sc1, sh1, wave * RN * 16, lane, sc, sh);
@@ -1285,7 +1096,7 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
   {
     constexpr int RN = k3N2 / 64;
     f32x4 acc[RN][MT];
-    zero_acc(acc);
+    zero_acc3(acc);
     gemm_split_rolled<RN, MT, k3N2 / 16>(buf, k3Ld, k3Plane, w2, wave_u * RN, k3N1 / 32, acc, lane);
     float4 sc[RN], sh[RN];
     load_affine4<RN>(sc2, sh2, wave * RN * 16, lane, sc, sh);
@@ -1299,7 +1110,7 @@ __global__ __launch_bounds__(256) void sa3_split_kernel(int b, const float *__re
   for (int pass = 0; pass < 2; ++pass) {                        // the wave's 12 column tiles, six at a time
     constexpr int RN = k3N3 / 128;
     f32x4 acc[RN][MT];
-    zero_acc(acc);
+    zero_acc3(acc);
     const int t0 = wave_u * 2 * RN + pass * RN;
     gemm_split_rolled<RN, MT, k3N3 / 16>(buf, k3Ld, k3Plane, w3, t0, k3N2 / 32, acc, lane);
     float4 sc[RN], sh[RN];
@@ -1341,9 +1152,9 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
   for (int i = tid; i < k3N2; i += 256) { aff[2 * k3N1 + i] = l2.scale[i]; aff[2 * k3N1 + k3N2 + i] = l2.shift[i]; }
   for (int i = tid; i < k3N3; i += 256) { aff[2 * (k3N1 + k3N2) + i] = l3.scale[i]; aff[2 * (k3N1 + k3N2) + k3N3 + i] = l3.shift[i]; }
   const float *sc1 = aff, *sh1 = aff + k3N1, *sc2 = aff + 2 * k3N1, *sh2 = sc2 + k3N2, *sc3 = aff + 2 * (k3N1 + k3N2), *sh3 = sc3 + k3N3;
-  const WStream w1 = make_stream<0>(l1.w, k3K0 * k3N1 * 6, 0, lane);
-  const WStream w2 = make_stream<0>(l2.w, k3N1 * k3N2 * 6, 0, lane);
-  const WStream w3 = make_stream<0>(l3.w, k3N2 * k3N3 * 6, 0, lane);
+  const WStream w1 = make_wstream(l1.w, k3K0 * k3N1 * 6, k3N1 / 16, 0, 0, lane);
+  const WStream w2 = make_wstream(l2.w, k3N1 * k3N2 * 6, k3N2 / 16, 0, 0, lane);
+  const WStream w3 = make_wstream(l3.w, k3N2 * k3N3 * 6, k3N3 / 16, 0, 0, lane);
   {   // operand: 64 rows x [feat(256), x, y, z, 0 ...]; all loads first, then split + LDS stores
     constexpr int IT = k4TM * 64 / 256;
     float4 val[IT];
@@ -1366,7 +1177,7 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
       const int e = tid + it * 256;
       const float v[4] = {val[it].x, val[it].y, val[it].z, val[it].w};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
       unsigned short *d = buf + (e >> 6) * k4LdIn + (e & 63) * 4;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * k4PlaneIn) = p[k];
@@ -1374,7 +1185,7 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
     if (tid < k4TM) {
       const float v[4] = {px, py, pz, 0.f};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         unsigned short *d = buf + k * k4PlaneIn + tid * k4LdIn + 256;
@@ -1388,7 +1199,7 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
   constexpr int MT = k4TM / 16;
   {   // layer 1: 288 -> 256, each wave 4 column tiles
     f32x4 acc[4][MT];
-    zero_acc(acc);
+    zero_acc3(acc);
     gemm_split_rolled<4, MT, k3N1 / 16>(buf, k4LdIn, k4PlaneIn, w1, wave_u * 4, k3K0 / 32, acc, lane);
     float4 sc[4], sh[4];
     load_affine4<4>(sc1, sh1, wave * 64, lane, sc, sh);
@@ -1400,9 +1211,9 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
   f32x4 acc2b[4][MT];
   {
     f32x4 acc2a[4][MT];
-    zero_acc(acc2a);
+    zero_acc3(acc2a);
     gemm_split_rolled<4, MT, k3N2 / 16>(buf, k4Ld, k4Plane, w2, wave_u * 4, k3N1 / 32, acc2a, lane);
-    zero_acc(acc2b);
+    zero_acc3(acc2b);
     gemm_split_rolled<4, MT, k3N2 / 16>(buf, k4Ld, k4Plane, w2, 16 + wave_u * 4, k3N1 / 32, acc2b, lane);
     float4 sc[4], sh[4];
     load_affine4<4>(sc2, sh2, wave * 64, lane, sc, sh);
@@ -1412,8 +1223,8 @@ __global__ __launch_bounds__(256, 1) void sa3_split4_kernel(int b, const float *
   __syncthreads();
   // layer 3 over the first K half (weight slabs 0..7), the wave's 12 column tiles as 6 + 6
   f32x4 acc3a[6][MT], acc3b[6][MT];
-  zero_acc(acc3a);
-  zero_acc(acc3b);
+  zero_acc3(acc3a);
+  zero_acc3(acc3b);
   const int t3 = wave_u * 12;
   gemm_split_rolled<6, MT, k3N3 / 16>(buf, k4Ld, k4Plane, w3, t3, 8, acc3a, lane, 0);
   gemm_split_rolled<6, MT, k3N3 / 16>(buf, k4Ld, k4Plane, w3, t3 + 6, 8, acc3b, lane, 0);
@@ -1512,9 +1323,9 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const float *sc1 = aff, *sh1 = aff + k3N1, *sc2 = aff + 2 * k3N1, *sh2 = sc2 + k3N2, *sc3 = aff + 2 * (k3N1 + k3N2), *sh3 = sc3 + k3N3;
-  const WStream w1 = make_stream<0>(l1.w, k3K0 * k3N1 * 6, 0, lane);
-  const WStream w2 = make_stream<0>(l2.w, k3N1 * k3N2 * 6, 0, lane);
-  const WStream w3 = make_stream<0>(l3.w, k3N2 * k3N3 * 6, 0, lane);
+  const WStream w1 = make_wstream(l1.w, k3K0 * k3N1 * 6, k3N1 / 16, 0, 0, lane);
+  const WStream w2 = make_wstream(l2.w, k3N1 * k3N2 * 6, k3N2 / 16, 0, 0, lane);
+  const WStream w3 = make_wstream(l3.w, k3N2 * k3N3 * 6, k3N3 / 16, 0, 0, lane);
   {   // operand: TM rows x [feat(256), x, y, z, 0 ...]; all loads first, then split + LDS stores
     constexpr int IT = TM * 64 / 256;
     float4 val[IT];
@@ -1537,7 +1348,7 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
       const int e = tid + it * 256;
       const float v[4] = {val[it].x, val[it].y, val[it].z, val[it].w};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
       unsigned short *d = buf + (e >> 6) * k4LdIn + (e & 63) * 4;
 #pragma unroll
       for (int k = 0; k < 3; ++k) *reinterpret_cast<uint2 *>(d + k * k4PlaneIn) = p[k];
@@ -1545,7 +1356,7 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
     if (tid < TM) {
       const float v[4] = {px, py, pz, 0.f};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         unsigned short *d = buf + k * k4PlaneIn + tid * k4LdIn + 256;
@@ -1558,7 +1369,7 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
   __syncthreads();
   {   // layer 1: 288 -> 256, each wave 4 column tiles
     f32x4 acc[4][MT];
-    zero_acc(acc);
+    zero_acc3(acc);
     gemm_split_rolled<4, MT, k3N1 / 16>(buf, k4LdIn, k4PlaneIn, w1, wave_u * 4, k3K0 / 32, acc, lane);
     float4 sc[4], sh[4];
     load_affine4<4>(sc1, sh1, wave * 64, lane, sc, sh);
@@ -1570,9 +1381,9 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
   f32x4 acc2b[4][MT];
   {
     f32x4 acc2a[4][MT];
-    zero_acc(acc2a);
+    zero_acc3(acc2a);
     gemm_split_rolled<4, MT, k3N2 / 16>(buf, k4Ld, k4Plane, w2, wave_u * 4, k3N1 / 32, acc2a, lane);
-    zero_acc(acc2b);
+    zero_acc3(acc2b);
     gemm_split_rolled<4, MT, k3N2 / 16>(buf, k4Ld, k4Plane, w2, 16 + wave_u * 4, k3N1 / 32, acc2b, lane);
     float4 sc[4], sh[4];
     load_affine4<4>(sc2, sh2, wave * 64, lane, sc, sh);
@@ -1582,8 +1393,8 @@ __device__ __forceinline__ void sa3_tile(const int *s_obj, unsigned short *buf, 
   __syncthreads();
   // layer 3 over the first K half (weight slabs 0..7), the wave's 12 column tiles as 6 + 6
   f32x4 acc3a[6][MT], acc3b[6][MT];
-  zero_acc(acc3a);
-  zero_acc(acc3b);
+  zero_acc3(acc3a);
+  zero_acc3(acc3b);
   const int t3 = wave_u * 12;
   gemm_split_rolled<6, MT, k3N3 / 16>(buf, k4Ld, k4Plane, w3, t3, 8, acc3a, lane, 0);
   gemm_split_rolled<6, MT, k3N3 / 16>(buf, k4Ld, k4Plane, w3, t3 + 6, 8, acc3b, lane, 0);
@@ -1727,7 +1538,7 @@ __device__ __forceinline__ void wave_layer(const unsigned short *wl, const bf16x
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
+      for (int p = 0; p < kPlanes; ++p)
         w[grp][i].v[p] = *reinterpret_cast<const bf16x8 *>(wp + ((grp * 2 + i) * 3 + p) * kFragS);
   };
   fetch(0);
@@ -1739,13 +1550,13 @@ __device__ __forceinline__ void wave_layer(const unsigned short *wl, const bf16x
     __builtin_amdgcn_sched_barrier(0);
     if (grp + 1 < NG) fetch(grp + 1);
     __builtin_amdgcn_sched_barrier(0);
-#define MSR3D_TERM(PW, PX)                                                                             \
+#define MSR3D_MMA(PW, PX)                                                                              \
     _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                      \
     _Pragma("unroll") for (int mt = 0; mt < 2; ++mt)                                                   \
         acc[t0 + i][mt] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[s][mt][PX], w[grp][i].v[PW], acc[t0 + i][mt], 0, 0, 0) \
                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[grp][i].v[PW], x[s][mt][PX], acc[t0 + i][mt], 0, 0, 0);
-    MSR3D_TERMS_ALL
-#undef MSR3D_TERM
+    MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
   }
 }
 
@@ -1764,7 +1575,7 @@ __device__ __forceinline__ void wave_next(const f32x4 (&acc)[NT][2], const float
       const float v[4] = {fmaxf(__builtin_fmaf(acc[t][mt][0], s4.x, h4.x), 0.f), fmaxf(__builtin_fmaf(acc[t][mt][1], s4.y, h4.y), 0.f),
                           fmaxf(__builtin_fmaf(acc[t][mt][2], s4.z, h4.z), 0.f), fmaxf(__builtin_fmaf(acc[t][mt][3], s4.w, h4.w), 0.f)};
       uint2 p[3];
-      split4(v, p);
+      sm_split4(v, p);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         unsigned *d = reinterpret_cast<unsigned *>(&x[t >> 1][mt][k]) + (t & 1) * 2;
@@ -1862,8 +1673,8 @@ __global__ __launch_bounds__(64 * k1Waves, 1) void sa1_split_kernel(int n, int m
       const float v0[4] = {pa[mt].x - cx, pa[mt].y - cy, pb[mt].x - cz, pb[mt].y};
       const float v1[4] = {pc[mt].x, pc[mt].y, 0.f, 0.f};
       uint2 p0[3], p1[3];
-      split4(v0, p0);
-      split4(v1, p1);
+      sm_split4(v0, p0);
+      sm_split4(v1, p1);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const uint4 q = g == 0 ? make_uint4(p0[k].x, p0[k].y, p1[k].x, p1[k].y) : make_uint4(0u, 0u, 0u, 0u);
@@ -2141,8 +1952,8 @@ __global__ __launch_bounds__(64 * k1RowsWaves, 1) void sa1_rows_kernel(int n, in
       const float v0[4] = {pa[mt].x - cx[mt], pa[mt].y - cy[mt], pb[mt].x - cz[mt], pb[mt].y};
       const float v1[4] = {pc[mt].x, pc[mt].y, 0.f, 0.f};
       uint2 p0[3], p1[3];
-      split4(v0, p0);
-      split4(v1, p1);
+      sm_split4(v0, p0);
+      sm_split4(v1, p1);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const uint4 q = g == 0 ? make_uint4(p0[k].x, p0[k].y, p1[k].x, p1[k].y) : make_uint4(0u, 0u, 0u, 0u);

@@ -69,8 +69,8 @@ constexpr int PITCH = KD + 16;          // bf16 units: 544 B rows, conflict-free
 constexpr int PLANE = TM * PITCH;       // bf16 units per plane
 constexpr int XS_BYTES = 3 * PLANE * 2; // 104,448
 constexpr int RING = 4;                 // weight pieces in flight per wave (12 KB)
-// the attention core's operand form: f32-input MFMA, or (MSR3D_TRAIN_PLANES = 1, the labelled bf16 variant) bf16 operands
-constexpr int kCoreMma = MSR3D_TRAIN_PLANES == 1 ? MSR3D_MMA_BF16 : MSR3D_MMA_F32;
+// the attention core's operand form: f32-input MFMA, or (MSR3D_SPLIT_TERMS = 1, the labelled bf16 variant) bf16 operands
+constexpr int kCoreMma = MSR3D_SPLIT_TERMS == 1 ? MSR3D_MMA_BF16 : MSR3D_MMA_F32;
 constexpr int MID_BYTES = 4 * 4 * 3 * 1024;   // FRAG planes of a 64 x 128 middle: 49,152
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -1053,8 +1053,8 @@ int msr3d_scene_block(const msr3d_scene_block_t *pp, msr3d_stream_t stream) {
   }
 }
 
-#if MSR3D_TRAIN_PLANES == 1
-// libmsr3d_hip_bf16.so (this file + wgrad_split.hip, MSR3D_TRAIN_PLANES = 1) carries the version of the header it was
+#if MSR3D_SPLIT_TERMS == 1
+// libmsr3d_hip_bf16.so (this file + wgrad_split.hip, MSR3D_SPLIT_TERMS = 1) carries the version of the header it was
 // compiled against: msr3d_amd/_lib.py::load_bf16 refuses a stale build (the main library exports this from pn2_ops.hip)
 int msr3d_abi_version(void) { return MSR3D_ABI_VERSION; }
 #endif

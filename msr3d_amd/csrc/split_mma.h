@@ -1,5 +1,6 @@
-// split_mma.h -- fp32-accurate matrix products on the bf16 matrix pipe, shared by the trainable part's
-// kernels (scene_block.hip, wgrad_split.hip).  Same arithmetic as sa_split.hip:
+// split_mma.h -- fp32-accurate matrix products on the bf16 matrix pipe: THE statement of the split arithmetic, shared
+// by the frozen encoder (sa_split.hip) and the trainable part's kernels (scene_block.hip, wgrad_split.hip,
+// rows_gemm_split.hip):
 //
 //     x = x0 + x1 + x2 (+e),  |e| <= 2^-27 |x|     (three bf16 terms, round-to-nearest-even residuals)
 //     x w ~ x0 w0 + x0 w1 + x1 w0 + x1 w1 + x0 w2 + x2 w0            (dropped: ~2^-26 |x w|)
@@ -29,19 +30,42 @@ typedef int sm_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPieceBytes = 3 * 1024;       // one (slab, tile): three planes of 64 lanes x 16 B
 
-// MSR3D_TRAIN_PLANES = 1 (python -m msr3d_amd.build builds libmsr3d_hip_bf16.so from scene_block.hip and wgrad_split.hip
-// with it): the LABELLED reduced variant MSR3D_TRAIN_MMA=bf16 of the trainable part -- every operand is its FIRST plane
-// only (= the value rounded to bf16, nearest even) and every product ONE v_mfma_f32_16x16x32_bf16 instead of six, fp32
-// accumulate; the attention core's QK^T / PV / backward products take bf16 operands as well (attn_core.h's bf16 operand
-// map).  Memory layouts are unchanged (the planes nobody reads are still written by their producers), so the two
-// libraries work on the same buffers.  Not fp32 accuracy: tests/test_train_bf16_gpu.py states the tolerance.
-#ifndef MSR3D_TRAIN_PLANES
-#define MSR3D_TRAIN_PLANES 3
+// MSR3D_SPLIT_TERMS: how many of the products are multiplied.  6 is the arithmetic above.  The other two are LABELLED
+// reduced variants, never the headline (python -m msr3d_amd.build builds a library of its own for each):
+//   3  libmsr3d_hip_split2.so from sa_split.hip, MSR3D_SA_MMA=split2 -- two bf16 terms per operand, the three products
+//      x0 w0 + x0 w1 + x1 w0 (~16 significant bits per product; the reference's cuDNN convolutions run TF32, 10 bits, by
+//      default on any Ampere-or-later GPU: README.md:81 pins torch 1.12.1 and nothing in the reference touches allow_tf32);
+//   1  libmsr3d_hip_bf16.so from scene_block.hip and wgrad_split.hip, MSR3D_TRAIN_MMA=bf16 -- every operand is its FIRST
+//      plane only (= the value rounded to bf16, nearest even) and every product ONE v_mfma_f32_16x16x32_bf16, fp32
+//      accumulate; the attention core's QK^T / PV / backward products take bf16 operands as well (attn_core.h's bf16
+//      operand map).  Not fp32 accuracy: tests/test_train_bf16_gpu.py states the tolerance.
+// Memory layouts are unchanged (the planes nobody reads are still written by their producers), so the libraries work on
+// the same buffers.
+#ifndef MSR3D_SPLIT_TERMS
+#define MSR3D_SPLIT_TERMS 6
 #endif
-#if MSR3D_TRAIN_PLANES != 3 && MSR3D_TRAIN_PLANES != 1
-#error "MSR3D_TRAIN_PLANES must be 3 or 1"
+#if MSR3D_SPLIT_TERMS != 6 && MSR3D_SPLIT_TERMS != 3 && MSR3D_SPLIT_TERMS != 1
+#error "MSR3D_SPLIT_TERMS must be 6, 3 or 1"
 #endif
-constexpr int kPlanes = MSR3D_TRAIN_PLANES;  // planes of an operand that are fetched and multiplied
+constexpr int kPlanes = MSR3D_SPLIT_TERMS == 6 ? 3 : MSR3D_SPLIT_TERMS == 3 ? 2 : 1;   // planes fetched and multiplied
+
+// The products of one block, SMALLEST first (the accumulator meets the big terms last), stated ONCE for every kernel:
+// MSR3D_SPLIT_EACH_TERM(F) expands to F(PA, PB) per product of plane PA of the first operand by plane PB of the second.
+// F is the user's statement macro and keeps its accumulator loops INSIDE, so that consecutive MFMAs hit different
+// accumulators.  (A macro on purpose: with a function template over a generic lambda, or a constexpr table of terms
+// under an unrolled loop, hipcc scheduled some kernels differently -- the rolled level-3 loops of sa_split.hip with
+// the first, scene_block.hip's and wgrad_split.hip's with the second.)
+#if MSR3D_SPLIT_TERMS == 6
+#define MSR3D_SPLIT_TERMS_GE6(...) __VA_ARGS__
+#else
+#define MSR3D_SPLIT_TERMS_GE6(...)
+#endif
+#if MSR3D_SPLIT_TERMS >= 3
+#define MSR3D_SPLIT_TERMS_GE3(...) __VA_ARGS__
+#else
+#define MSR3D_SPLIT_TERMS_GE3(...)
+#endif
+#define MSR3D_SPLIT_EACH_TERM(F) MSR3D_SPLIT_TERMS_GE6(F(2, 0) F(0, 2) F(1, 1)) MSR3D_SPLIT_TERMS_GE3(F(1, 0) F(0, 1)) F(0, 0)
 
 // ---- exact three-way split -----------------------------------------------------------------------------
 __device__ __forceinline__ unsigned sm_pk_bf16(float a, float b) {       // v_cvt_pk_bf16_f32 (RNE)
@@ -93,8 +117,15 @@ __device__ __forceinline__ void sm_split1(float v, unsigned short (&p)[3]) {
 }
 
 // ---- the PACK stream --------------------------------------------------------------------------------------
+// One PIECE = one (slab, column tile): three planes, 3 x 1 KB coalesced reads per wave.  Pieces are consumed in
+// (slab, tile) order and fetched D pieces ahead through a register ring, so a wave keeps D x 3 KB in flight whatever
+// the operand's width (tools/probe/l2_stream.hip: the L2 -> CU stream needs >= 8 loads in flight per wave to pass
+// 30 B/clk/CU).
 struct WPiece { bf16x8 v[3]; };
 
+// The stream goes through a buffer descriptor: wave-uniform base (SGPRs) + one per-lane byte offset + an SGPR piece
+// offset.  With flat loads hipcc materialises every piece's 64-bit address in its own VGPR pair and hoists them all
+// out of a persistent loop (~180 VGPRs, all spilled).
 struct WStream {
   __amdgpu_buffer_rsrc_t rsrc;
   int voff;                        // lane * 16
@@ -111,18 +142,20 @@ __device__ __forceinline__ WStream make_wstream(const unsigned short *pack, unsi
   st.nt = nt;
   return st;
 }
+// NT: the column tiles per slab as a compile-time constant (0: st.nt) -- rolled loops fold it into their offsets
+template <int NT = 0>
 __device__ __forceinline__ void load_wpiece(WPiece &f, const WStream &st, int s, int rn) {
-  const int piece = st.soff + (s * st.nt + rn) * kPieceBytes;
+  const int piece = st.soff + (s * (NT ? NT : st.nt) + rn) * kPieceBytes;
 #pragma unroll
   for (int p = 0; p < kPlanes; ++p) {
     const sm_i32x4 r = __builtin_amdgcn_raw_buffer_load_b128(st.rsrc, st.voff, piece + p * 1024, 0);
     f.v[p] = *reinterpret_cast<const bf16x8 *>(&r);
   }
 }
-template <int RN, int D>
+template <int RN, int D, int NT = 0>
 __device__ __forceinline__ void preload_wring(WPiece (&ring)[D], const WStream &st) {
 #pragma unroll
-  for (int q = 0; q < D; ++q) load_wpiece(ring[q], st, q / RN, q % RN);
+  for (int q = 0; q < D; ++q) load_wpiece<NT>(ring[q], st, q / RN, q % RN);
 }
 
 // ---- X fragment sources in LDS ------------------------------------------------------------------------------
@@ -161,7 +194,7 @@ __device__ __forceinline__ int frag_off4(int mt, int j, int c, int p) {
 // acc[rn][mt] (+)= Op[tile rn] . X[tile mt]^T over KS slabs of 32.  W_FIRST: D = W X^T (lane (j, g) holds
 // operand rows 4 g + r of token j); otherwise D = X W^T (lane (j, g) holds tokens 4 g + r of operand row j).
 // `ring` holds pieces 0..D-1 on entry.  MT0: first row tile of X this wave works on.
-template <bool W_FIRST, int RN, int MT, int KS, int D, typename XF>
+template <bool W_FIRST, int RN, int MT, int KS, int D, int NT = 0, typename XF>
 __device__ __forceinline__ void gemm_split3(const XF &xf, int mt0, const WStream &wg, f32x4 (&acc)[RN][MT],
                                             const WPiece (&ring)[D]) {
   constexpr int NP = KS * RN;
@@ -174,7 +207,7 @@ __device__ __forceinline__ void gemm_split3(const XF &xf, int mt0, const WStream
   for (int q = 0; q < NP; ++q) {
     const int s = q / RN, rn = q % RN;
     __builtin_amdgcn_sched_barrier(0);          // this piece's fetches stay below the previous piece's MFMAs ..
-    if (q + D < NP) load_wpiece(w[q + D], wg, (q + D) / RN, (q + D) % RN);
+    if (q + D < NP) load_wpiece<NT>(w[q + D], wg, (q + D) / RN, (q + D) % RN);
     if (rn == 0) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -182,19 +215,12 @@ __device__ __forceinline__ void gemm_split3(const XF &xf, int mt0, const WStream
         for (int p = 0; p < kPlanes; ++p) x[mt][p] = xf(mt0 + mt, s, p);
     }
     __builtin_amdgcn_sched_barrier(0);          // .. and above its own
-#define MSR3D_TERM(PW, PX)                                                                                  \
+#define MSR3D_MMA(PW, PX)                                                                                   \
     _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                       \
         acc[rn][mt] = W_FIRST ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[q].v[PW], x[mt][PX], acc[rn][mt], 0, 0, 0) \
                               : __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[mt][PX], w[q].v[PW], acc[rn][mt], 0, 0, 0);
-#if MSR3D_TRAIN_PLANES == 3
-    MSR3D_TERM(2, 0)
-    MSR3D_TERM(0, 2)
-    MSR3D_TERM(1, 1)
-    MSR3D_TERM(1, 0)
-    MSR3D_TERM(0, 1)
-#endif
-    MSR3D_TERM(0, 0)
-#undef MSR3D_TERM
+    MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
   }
 }
 

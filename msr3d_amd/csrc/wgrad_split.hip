@@ -259,19 +259,12 @@ __device__ __forceinline__ void wgrad_tile(const WP &pr, int ntile, int ktile, u
           fb[b][ORD_B[q]] = *reinterpret_cast<const bf16x8 *>(Bs + (2 * wc + b) * TILE_BYTES + ORD_B[q] * 1024);
       }
       __builtin_amdgcn_sched_barrier(0);
-#define MSR3D_TERM(PA, PB)                                                                       \
+#define MSR3D_MMA(PA, PB)                                                                        \
       _Pragma("unroll") for (int a = 0; a < 4; ++a)                                              \
       _Pragma("unroll") for (int b = 0; b < 2; ++b)                                              \
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][PA], fb[b][PB], acc[a][b], 0, 0, 0);
-#if MSR3D_TRAIN_PLANES == 3
-      MSR3D_TERM(2, 0)
-      MSR3D_TERM(0, 2)
-      MSR3D_TERM(1, 1)
-      MSR3D_TERM(1, 0)
-      MSR3D_TERM(0, 1)
-#endif
-      MSR3D_TERM(0, 0)
-#undef MSR3D_TERM
+      MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
     }
     WG_STAMP(5);
     WG_PUT(1, tw);
@@ -481,19 +474,12 @@ __device__ __forceinline__ void wgrad_tile_pipe(const WP &pr, int ntile, int kti
         for (int q = 0; q < 3; ++q) asm volatile("" ::"v"(fa[a][q]), "v"(fb[a][q]));
       return;
 #endif
-#define MSR3D_TERM(PA, PB)                                                                       \
+#define MSR3D_MMA(PA, PB)                                                                        \
       _Pragma("unroll") for (int a = 0; a < 2; ++a)                                              \
       _Pragma("unroll") for (int b = 0; b < 2; ++b)                                              \
           acc[2 * half + a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a][PA], fb[b][PB], acc[2 * half + a][b], 0, 0, 0);
-#if MSR3D_TRAIN_PLANES == 3
-      MSR3D_TERM(2, 0)
-      MSR3D_TERM(0, 2)
-      MSR3D_TERM(1, 1)
-      MSR3D_TERM(1, 0)
-      MSR3D_TERM(0, 1)
-#endif
-      MSR3D_TERM(0, 0)
-#undef MSR3D_TERM
+      MSR3D_SPLIT_EACH_TERM(MSR3D_MMA)
+#undef MSR3D_MMA
     };
 
     Slab g0, g1;                                   // fetched rows of the slabs two and three ahead of the multiply

@@ -93,26 +93,31 @@ def _pack_layer(conv, bn, kp, feat_first):
 _KP0_SPLIT = (32, 160, 288)
 
 
-def _pack_layer_split(conv, bn, kp, feat_first, kperm=False):
-    """Parameters for msr3d_sa_level_split: the weight split exactly into three bf16 terms, packed in
-    16x16x32 MFMA-fragment order, and the folded BN affine (fp32).
-    kperm: the K axis of each 32-wide slab numbered the way the previous layer's accumulators lie in the
-    lanes (level 1 keeps its activations in registers: csrc/sa_split.hip) -- fragment position (g, e) of
-    slab s holds channel 32 s + 16 (e >> 2) + 4 g + (e & 3)."""
-    flat = _pack_rows(conv, bn, kp, feat_first)
-    wp, scale, shift = flat
-    n = wp.shape[0]
-    if kperm:
-        k = torch.arange(kp, device=wp.device)
-        s_, g_, e_ = k // 32, (k % 32) // 8, k % 8
-        wp = wp[:, 32 * s_ + 16 * (e_ >> 2) + 4 * g_ + (e_ & 3)]
+def _split_frag(wp):
+    """A (n, kp) fp32 weight split exactly into three bf16 terms (round-to-nearest-even residuals), packed in
+    16x16x32 MFMA-fragment order [kp/32 slabs][n/16 tiles][3 planes][64 lanes = 16 g + i][8] (csrc/split_mma.h: PACK)."""
+    n, kp = wp.shape
     w0 = wp.to(torch.bfloat16)
     r1 = wp - w0.float()
     w1 = r1.to(torch.bfloat16)
     w2 = (r1 - w1.float()).to(torch.bfloat16)
     planes = torch.stack([w0, w1, w2])                                   # (3, n, kp)
     frag = planes.view(3, n // 16, 16, kp // 32, 4, 8).permute(3, 1, 0, 4, 2, 5)   # (s, t, p, g, i, j)
-    return frag.contiguous().reshape(-1), torch.cat([scale, shift]).contiguous()
+    return frag.contiguous().reshape(-1)
+
+
+def _pack_layer_split(conv, bn, kp, feat_first, kperm=False):
+    """Parameters for msr3d_sa_level_split: the weight in split fragment form (_split_frag) and the folded BN
+    affine (fp32).
+    kperm: the K axis of each 32-wide slab numbered the way the previous layer's accumulators lie in the
+    lanes (level 1 keeps its activations in registers: csrc/sa_split.hip) -- fragment position (g, e) of
+    slab s holds channel 32 s + 16 (e >> 2) + 4 g + (e & 3)."""
+    wp, scale, shift = _pack_rows(conv, bn, kp, feat_first)
+    if kperm:
+        k = torch.arange(kp, device=wp.device)
+        s_, g_, e_ = k // 32, (k % 32) // 8, k % 8
+        wp = wp[:, 32 * s_ + 16 * (e_ >> 2) + 4 * g_ + (e_ & 3)]
+    return _split_frag(wp), torch.cat([scale, shift]).contiguous()
 
 
 def _pack_level2_first(conv, bn):
@@ -120,19 +125,10 @@ def _pack_level2_first(conv, bn):
     the three coordinate columns as fp32 rows (128, 4) appended to the affine -- the kernel adds their
     contribution to the accumulators with fp32 FMAs instead of a fifth, 29/32-empty slab of MFMAs."""
     w = conv.weight.detach().reshape(conv.out_channels, conv.in_channels).float()      # K order [xyz, features]
-    n = w.shape[0]
-    feat = w[:, 3:].contiguous()
-    w0 = feat.to(torch.bfloat16)
-    r1 = feat - w0.float()
-    w1 = r1.to(torch.bfloat16)
-    w2 = (r1 - w1.float()).to(torch.bfloat16)
-    planes = torch.stack([w0, w1, w2])
-    kp = feat.shape[1]
-    frag = planes.view(3, n // 16, 16, kp // 32, 4, 8).permute(3, 1, 0, 4, 2, 5)       # (s, t, p, g, i, j)
     _, scale, shift = _pack_rows(conv, bn, conv.in_channels, False)
-    wxyz = torch.zeros((n, 4), device=w.device)
+    wxyz = torch.zeros((w.shape[0], 4), device=w.device)
     wxyz[:, :3] = w[:, :3]
-    return frag.contiguous().reshape(-1), torch.cat([scale, shift, wxyz.reshape(-1)]).contiguous()
+    return _split_frag(w[:, 3:].contiguous()), torch.cat([scale, shift, wxyz.reshape(-1)]).contiguous()
 
 
 def _state_key(net):

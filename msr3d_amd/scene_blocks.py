@@ -22,7 +22,7 @@ PIECE = 3 * 1024          # bytes of one (slab, tile): three planes of 64 lanes 
 #   "f32"   (default) every product as six bf16 MFMA products of exactly split operands: fp32 accuracy
 #   "bf16"  LABELLED reduced variant (MSR3D_TRAIN_MMA=bf16): operands rounded to bf16, ONE MFMA product per product, fp32
 #           accumulate, fp32 storage of every activation -- what `torch.autocast(bfloat16)` linears compute; the kernels are
-#           the same sources compiled with MSR3D_TRAIN_PLANES=1 (libmsr3d_hip_bf16.so).  Never the headline.
+#           the same sources compiled with MSR3D_SPLIT_TERMS=1 (libmsr3d_hip_bf16.so).  Never the headline.
 _TRAIN_MMA = [os.environ.get("MSR3D_TRAIN_MMA", "f32")]
 if _TRAIN_MMA[0] not in ("f32", "bf16"):
     raise ValueError("MSR3D_TRAIN_MMA must be 'f32' or 'bf16'")

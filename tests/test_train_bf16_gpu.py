@@ -1,5 +1,5 @@
 """The LABELLED reduced variant of the trainable part, MSR3D_TRAIN_MMA=bf16 (scene_blocks.set_train_mma("bf16"),
-libmsr3d_hip_bf16.so = csrc/scene_block.hip + csrc/wgrad_split.hip compiled with MSR3D_TRAIN_PLANES=1): operands rounded
+libmsr3d_hip_bf16.so = csrc/scene_block.hip + csrc/wgrad_split.hip compiled with MSR3D_SPLIT_TERMS=1): operands rounded
 to bf16, ONE v_mfma_f32_16x16x32_bf16 per product instead of six, fp32 accumulate, fp32 storage -- the "bf16 MFMA tiles,
 stated tolerance" form north_star names for the object attention (/root/reference/modules/layers/transformers.py:200-252)
 and the projector.  Pinned against the reference-generated full-size fixtures at BASELINE.md's tolerance for a bf16 path:
