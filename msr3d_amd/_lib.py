@@ -282,6 +282,18 @@ def exported_symbols():
 ABI_VERSION = 37       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
+def _check_abi(lib, path, may_lack_version=False):
+    """A library built from another header version is refused: the entry points' arguments may have moved."""
+    ver = getattr(lib, "msr3d_abi_version", None) if may_lack_version else lib.msr3d_abi_version
+    if ver is not None:
+        ver.restype = _c_int
+    have = ver() if ver is not None else "none (pre-v27 build)"
+    if have != ABI_VERSION:
+        raise ImportError(
+            f"msr3d_amd: {path} has ABI version {have}, this package binds version {ABI_VERSION} "
+            "(include/msr3d_hip.h). Rebuild it with `python -m msr3d_amd.build`.")
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -296,11 +308,7 @@ def load():
         raise ImportError(
             f"msr3d_amd: cannot load {LIB_PATH} ({e}). Build it with `python -m msr3d_amd.build`; "
             "there is no CPU fallback.") from e
-    lib.msr3d_abi_version.restype = _c_int
-    if lib.msr3d_abi_version() != ABI_VERSION:
-        raise ImportError(
-            f"msr3d_amd: {LIB_PATH} has ABI version {lib.msr3d_abi_version()}, this package binds "
-            f"version {ABI_VERSION} (include/msr3d_hip.h). Rebuild it with `python -m msr3d_amd.build`.")
+    _check_abi(lib, LIB_PATH)
     lib.msr3d_sqdist_contract.restype = _c_int
     lib.msr3d_wgrad_form.restype = _c_int
     lib.msr3d_wgrad_form.argtypes = [_c_int]
@@ -316,8 +324,8 @@ def load():
     return lib
 
 
-_BLK_NAMES = {0: "attn_fwd", 1: "ffn_fwd", 2: "ffn_bwd", 3: "attn_bwd", 4: "linear", 5: "linear_ksplit"}
-_PRO_NAMES = {0: "plain", 1: "add", 2: "ln", 3: "ln2", 4: "lnbwd", 5: "ln2bwd"}
+_BLK_NAMES = {v: k for k, v in BLK.items()}
+_PRO_NAMES = {v: k for k, v in PRO.items()}
 
 
 class _Entry:
@@ -364,14 +372,7 @@ def load_split2():
         if not os.path.exists(_build.LIB_SPLIT2):
             _build.build()
         lib = ctypes.CDLL(_build.LIB_SPLIT2)
-        ver = getattr(lib, "msr3d_abi_version", None)
-        if ver is not None:
-            ver.restype = _c_int
-        if ver is None or ver() != ABI_VERSION:
-            # built from an older header: the entry points' arguments may have moved
-            raise ImportError(
-                f"msr3d_amd: {_build.LIB_SPLIT2} has ABI version {ver() if ver is not None else 'none (pre-v27 build)'}, this "
-                f"package binds version {ABI_VERSION} (include/msr3d_hip.h). Rebuild it with `python -m msr3d_amd.build`.")
+        _check_abi(lib, _build.LIB_SPLIT2, may_lack_version=True)
         lib.msr3d_set_reserved_cus.argtypes = [_c_int]
         lib.msr3d_set_reserved_cus.restype = _c_int
         if _reserved_cus[0]:                         # (its kernels size their grids from their OWN copy of the setting)
@@ -401,11 +402,7 @@ def load_bf16():
         if not os.path.exists(_build.LIB_BF16):
             _build.build()
         lib = ctypes.CDLL(_build.LIB_BF16)
-        lib.msr3d_abi_version.restype = _c_int
-        if lib.msr3d_abi_version() != ABI_VERSION:
-            raise ImportError(
-                f"msr3d_amd: {_build.LIB_BF16} has ABI version {lib.msr3d_abi_version()}, this package binds version "
-                f"{ABI_VERSION} (include/msr3d_hip.h). Rebuild it with `python -m msr3d_amd.build`.")
+        _check_abi(lib, _build.LIB_BF16)
         lib.msr3d_wgrad_form.restype = _c_int
         lib.msr3d_wgrad_form.argtypes = [_c_int]
         for name in _BF16_ENTRIES:
@@ -445,9 +442,36 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
-def call(name, *args):
-    """Call entry point `name` of the loaded library; a non-zero status raises."""
-    check(getattr(load(), name)(*args), name)
+def call(name, *args, lib=None):
+    """Call entry point `name` of the loaded library (or of `lib`, a variant library); a non-zero status raises."""
+    check(getattr(lib or load(), name)(*args), name)
+
+
+def fill(s, fields):
+    """Set the fields of a ctypes struct from a dict -- or those of an array of structs from a list of dicts: a tensor
+    gives its data pointer, a c_void_p its value, None is NULL.  -> s"""
+    if isinstance(s, ctypes.Array):
+        for q, kw in zip(s, fields):
+            fill(q, kw)
+        return s
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            v = v.data_ptr()
+        elif isinstance(v, _ptr):
+            v = v.value
+        setattr(s, k, v if v is not None else 0)
+    return s
+
+
+def launch(name, s, stream, lib=None):
+    """Call entry point `name` on a filled struct (passed by reference) or an array of them (passed as count, array);
+    a non-zero status raises with the non-zero fields in the message."""
+    many = isinstance(s, ctypes.Array)
+    rc = getattr(lib or load(), name)(*((len(s), s) if many else (ctypes.byref(s),)), stream)
+    if rc:
+        fields = "; ".join(", ".join(f"{n}={getattr(q, n)!r}" for n, _ in q._fields_ if getattr(q, n))
+                           for q in (s if many else (s,)))
+        check(rc, f"{name}({fields})")
 
 
 # ---------------------------------------------------------------------------------------

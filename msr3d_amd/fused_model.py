@@ -144,7 +144,7 @@ class PrompterSchedule:
                     and d.get("anchor_locs") is not None and d.get("anchor_orientation") is not None
                     and (not pr.use_orientation or pr.orientation_encoder.in_features == 84)):   # 4 + 8 x 10 bands
                 return False
-        # msr3d_pos_embed_bwd sums the positional gradient of at most three layers; the mask is read as bytes
+        # the positional backward (_front_bwd) sums the positional gradient of at most three layers; the mask is read as bytes
         if not 1 <= len(pr.spatial_encoder) <= 3:
             return False
         msk = d.get("obj_masks")
@@ -344,7 +344,7 @@ class PrompterSchedule:
                 wg.add(a["d_xacc0"].data_ptr(), L * D, D, a["qf"].data_ptr(), QF, QF, dm["B"], oe.weight.grad.data_ptr(), QF,
                        oe.bias.grad.data_ptr())
             # x = the features with a zero row per agent: those rows add nothing to dW; the bias gradient (object rows
-            # only) comes from msr3d_anchor_front_bwd
+            # only) comes from the positional backward (_front_bwd)
             self.wg_proj = wg.add(a["d_xacc0"].data_ptr(), D, D, a["e61"].data_ptr(), KE, KE, M, lpj.weight.grad.data_ptr(),
                                   KE, 0)
         else:
@@ -357,19 +357,14 @@ class PrompterSchedule:
                                   lpj.bias.grad.data_ptr())
         self.packs, self.wgrad = pk, wg
 
-    def forward_blocks(self, embeds):
-        """forward   step_begin | pack | proj | pos | 3 x [rows | attention block | rows | feed-forward block]
-                     | rows | llm_proj        (rows = msr3d_scene_rows: sum of the partial slabs + the row-local
-                     dropout / residual / LayerNorm chain, once per row, -> bf16 planes)"""
-        pr, m, a, dm = self.pr, self.model, self.arena, self.dims
-        B, L, M, D, W, H, FF, E, KF, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E", "KF", "KE", "nl"))
-        dev = embeds.device
-        self.lib = lib = _lib.load()
-        self.stream = st = _lib.current_stream_ptr(dev)
-        train = m.training
-        seed = hipops.seed_word(dev)
-        anchor = self.anchor
-        if anchor:
+    # ------------------------------------------------------------------ steps the walks share
+    def _begin(self, embeds):
+        """What every forward walk opens with: the launch stream, the staged feature matrix (-> saved_embeds, returned) and
+        each layer's four dropout salts and probabilities (attention, dropout1, dropout2, feed-forward)."""
+        a, dm = self.arena, self.dims
+        B, L, M, KE = (dm[k] for k in ("B", "L", "M", "KE"))
+        self.stream = _lib.current_stream_ptr(embeds.device)
+        if self.anchor:
             # object features behind a zero agent row per scene (one strided copy; the agent rows are never written)
             a["e61"].view(B, L, KE)[:, 1:].copy_(embeds.reshape(B, L - 1, KE))
             e2 = a["e61"]
@@ -377,13 +372,109 @@ class PrompterSchedule:
             e2 = embeds.reshape(M, KE)
             e2 = e2 if e2.is_contiguous() else e2.contiguous()
         self.saved_embeds = e2
-        layers = list(pr.spatial_encoder)
+        layers, train = list(self.pr.spatial_encoder), self.model.training
         self.salts = [[hipops._next_salt() for _ in range(4)] for _ in layers]
-        self.ps = []
-        for layer in layers:
-            sa = layer.self_attn
-            self.ps.append((float(sa.dropout.p) if train else 0.0, float(layer.dropout1.p) if train else 0.0,
-                            float(layer.dropout2.p) if train else 0.0, float(layer.dropout.p) if train else 0.0))
+        self.ps = [tuple(float(d.p) if train else 0.0
+                         for d in (layer.self_attn.dropout, layer.dropout1, layer.dropout2, layer.dropout)) for layer in layers]
+        return e2
+
+    def _step_begin(self):
+        """The arena's zero fill (+ the seed bump) as a launch of its own."""
+        a = self.arena
+        _lib.call("msr3d_step_begin", _ptr(a.buf), a.zero_floats,
+                  _ptr(hipops.seed_word(a.buf.device)) if self.bump_seed else None, self.stream)
+
+    def _front(self, e2, planes, tokens):
+        """Object projection -> x0 (the agent's orientation term, one row per scene, rides in its launch), then ONE positional
+        launch.  Agent token: agent / object rows assembled, LN(loc_layers[0]) added -> xin0.  Otherwise the positional
+        term, and with `tokens` also the layer input (tokens + positional term + the two constant rows) -> xin0.  `planes`:
+        xin0 as the first block's bf16 planes as well, or None."""
+        pr, a, dm, st = self.pr, self.arena, self.dims, self.stream
+        B, L, M, D, KF, KE = (dm[k] for k in ("B", "L", "M", "D", "KF", "KE"))
+        lp = pr.obj_linear_projection
+        front = [dict(a_kc=1, b_kc=1, M=M, N=D, K=KE, A=e2, lda=KE, B=lp.weight, ldb=KE, C=a["x0"], ldc=D,
+                      bias=lp.bias, beta=1.0)]
+        if self.anchor and pr.use_orientation:
+            oe = pr.orientation_encoder
+            front.append(dict(a_kc=1, b_kc=1, M=B, N=D, K=oe.in_features, A=a["qf"], lda=oe.in_features, B=oe.weight,
+                              ldb=oe.in_features, C=a["a_ori"], ldc=D, bias=oe.bias, beta=1.0))
+        self._multi(front)
+        type_w = _ptr(pr.object_type_embedding.weight)
+        ori = _ptr(pr.object_orientation_feat) if pr.use_orientation else None
+        if self.anchor:
+            ll = pr.loc_layers[0]
+            _lib.call("msr3d_anchor_front_fwd", B, L, _ptr(a["x0"]), _ptr(a["a_ori"]), _ptr(pr.anchor_feat), type_w, ori,
+                      _ptr(a["loc6"]), _ptr(ll[0].weight), _ptr(ll[0].bias), _ptr(ll[1].weight), _ptr(ll[1].bias),
+                      ctypes.c_float(ll[1].eps), _ptr(a["pos"]), _ptr(a["sa"]), _ptr(a["sta"]), _ptr(a["xin0"]),
+                      _ptr(planes), st)
+            return
+        le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
+        enc = (_ptr(a["ff"]), _ptr(a["loc6"]), _ptr(le[0].weight), _ptr(le[0].bias), _ptr(le[1].weight), _ptr(le[1].bias),
+               ctypes.c_float(le[1].eps), _ptr(se[0].weight), _ptr(se[0].bias), _ptr(se[1].weight), _ptr(se[1].bias),
+               ctypes.c_float(se[1].eps), _ptr(a["pos"]), _ptr(a["sa"]), _ptr(a["sta"]), _ptr(a["sb"]), _ptr(a["stb"]))
+        if tokens:
+            _lib.call("msr3d_pos_embed_tokens_fwd", M, L, KF, *enc, _ptr(a["x0"]), type_w, ori, _ptr(a["xin0"]),
+                      _ptr(planes), st)
+        else:
+            _lib.call("msr3d_pos_embed_fwd", M, KF, *enc, st)
+
+    def _front_bwd(self, stem):
+        """Backward of the positional launch over the layer-input gradients `stem`0 .. (d_xacc | d_xin: every layer's with
+        obj_loc_encoding 'same_all', the first layer's otherwise)."""
+        pr, a, dm, st = self.pr, self.arena, self.dims, self.stream
+        B, L, M, D, nl = (dm[k] for k in ("B", "L", "M", "D", "nl"))
+        more = pr.cfg.spatial_encoder.obj_loc_encoding == "same_all" and nl > 1
+        d_x = (_ptr(a[stem + "0"]), _ptr(a[stem + "1"]) if more else None, _ptr(a[stem + "2"]) if (more and nl > 2) else None)
+        tg = pr.object_type_embedding.weight.grad
+        d_ori = _ptr(pr.object_orientation_feat.grad) if pr.use_orientation else None
+        if self.anchor:
+            ll = pr.loc_layers[0]
+            _lib.call("msr3d_anchor_front_bwd", B, L, *d_x, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(ll[1].weight),
+                      _ptr(a["d_la"]), _ptr(ll[1].weight.grad), _ptr(ll[1].bias.grad), _ptr(tg), d_ori,
+                      _ptr(pr.obj_linear_projection.bias.grad), _ptr(tg, D), _ptr(pr.anchor_feat.grad), st)
+        else:
+            le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
+            _lib.call("msr3d_pos_embed_bwd", M, *d_x, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(le[1].weight), _ptr(a["sb"]),
+                      _ptr(a["stb"]), _ptr(se[1].weight), _ptr(a["d_la"]), _ptr(a["d_lb"]), _ptr(le[1].weight.grad),
+                      _ptr(le[1].bias.grad), _ptr(se[1].weight.grad), _ptr(se[1].bias.grad), _ptr(tg), d_ori, st)
+
+    def _qkvc(self, t):
+        """The q | k | v | cond column blocks of a (tokens, W) matrix with their row strides, as the attention kernels take them."""
+        D, W, base = self.dims["D"], self.dims["W"], t.data_ptr()
+        return _vp(base), _vp(base + 4 * D), _vp(base + 8 * D), W, _vp(base + 12 * D), W
+
+    def _attention_fwd(self, i):
+        """Layer i's attention core on the strip kernel: qkvc{i} -> ctx{i}, probs{i}."""
+        a, dm = self.arena, self.dims
+        _lib.call("msr3d_spatial_attn_fwd", dm["B"], dm["L"], dm["H"], dm["D"] // dm["H"], 5, *self._qkvc(a[f"qkvc{i}"]),
+                  _ptr(a["pw"]), _ptr(self.pad), _ptr(a[f"ctx{i}"]), _ptr(a[f"probs{i}"]),
+                  hipops.attention_mma(False, training=True), self.stream)
+
+    def _attention_bwd(self, i, d_qkvc):
+        """Its backward: d_ctx -> d_qkvc."""
+        a, dm = self.arena, self.dims
+        _lib.call("msr3d_spatial_attn_bwd", dm["B"], dm["L"], dm["H"], dm["D"] // dm["H"], 5, *self._qkvc(a[f"qkvc{i}"]),
+                  _ptr(a["pw"]), _ptr(self.pad), _ptr(a[f"probs{i}"]), _ptr(a["d_ctx"]), *self._qkvc(d_qkvc),
+                  hipops.attention_mma(True), self.stream)
+
+    def _norm2(self, i, out):
+        """Fields of the launch that closes layer i, rows or strip: dropout2 of the feed-forward sum, + the residual t{i},
+        LayerNorm(norm2) -> s3_{i}, st3_{i} and `out`."""
+        a, norm = self.arena, self.pr.spatial_encoder[i].norm2
+        return dict(pro=PRO["ln"], a1=a[f"t{i}"], g1=norm.weight, b1=norm.bias, eps1=norm.eps, p1=self.ps[i][2],
+                    salt1=self.salts[i][2], seed=hipops.seed_word(a.buf.device), o0=a[f"s3_{i}"], ost1=a[f"st3_{i}"], o1=out)
+
+    def forward_blocks(self, embeds):
+        """forward   step_begin | pack | proj | pos | 3 x [rows | attention block | rows | feed-forward block]
+                     | rows | llm_proj        (rows = msr3d_scene_rows: sum of the partial slabs + the row-local
+                     dropout / residual / LayerNorm chain, once per row, -> bf16 planes)"""
+        pr, m, a, dm = self.pr, self.model, self.arena, self.dims
+        B, L, M, D, W, H, FF, E = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E"))
+        dev = embeds.device
+        seed = hipops.seed_word(dev)
+        e2 = self._begin(embeds)
+        st = self.stream
+        layers = list(pr.spatial_encoder)
         same_all = pr.cfg.spatial_encoder.obj_loc_encoding == "same_all"
         pk, xp, part, MD = self.packs, self.xp, a["part"], M * D
         hyb = self.hybrid
@@ -394,70 +485,37 @@ class PrompterSchedule:
             scene_blocks.launch_block(st_, rows_total=RT, **kw)
         rows = scene_blocks.launch_rows
         nff = FF // 128
+
+        def close(i, out, **kw):        # layer i's closing norm over the sum of its feed-forward block's partial slabs
+            rows(st, M=M, L=Lt, part=part, nslab=nff, part_stride=MD, a0_bias=layers[i].linear2.bias,
+                 sum_out=a[f"ffn{i}"], **self._norm2(i, out), **kw)
         join = None
         with torch.cuda.device(dev):
-            if _PACK_FORK:
-                rc = lib.msr3d_step_begin(_ptr(a.buf), a.zero_floats, _ptr(seed) if self.bump_seed else None, st)
-                _lib.check(rc, "msr3d_step_begin")
-                if self._pack_stream is None:
-                    self._pack_stream = torch.cuda.Stream(device=dev)
-                side = self._pack_stream
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    pk.launch(_lib.current_stream_ptr(dev))
-                join = side
-            elif _MERGE:
+            if _MERGE and not _PACK_FORK:
                 # ONE launch: this step's weights split and fragment-packed + the arena's zero fill + the seed bump
                 pk.launch(st, begin=(a.buf, a.zero_floats, seed if self.bump_seed else None))
             else:
-                rc = lib.msr3d_step_begin(_ptr(a.buf), a.zero_floats, _ptr(seed) if self.bump_seed else None, st)
-                _lib.check(rc, "msr3d_step_begin")
-                pk.launch(st)
-            lp = pr.obj_linear_projection
-            front = [dict(a_kc=1, b_kc=1, M=M, N=D, K=KE, A=e2, lda=KE, B=lp.weight, ldb=KE, C=a["x0"], ldc=D,
-                          bias=lp.bias, beta=1.0)]
-            if anchor:
-                if pr.use_orientation:       # the agent's orientation term, one row per scene, in the projection's launch
-                    oe = pr.orientation_encoder
-                    front.append(dict(a_kc=1, b_kc=1, M=B, N=D, K=oe.in_features, A=a["qf"], lda=oe.in_features, B=oe.weight,
-                                      ldb=oe.in_features, C=a["a_ori"], ldc=D, bias=oe.bias, beta=1.0))
-                self._multi(front)
-                ll = pr.loc_layers[0]
-                # agent / object rows assembled, LN(loc_layers[0]) added, -> xin0 and the first block's planes: one launch
-                rc = lib.msr3d_anchor_front_fwd(B, L, _ptr(a["x0"]), _ptr(a["a_ori"]), _ptr(pr.anchor_feat),
-                                                _ptr(pr.object_type_embedding.weight),
-                                                _ptr(pr.object_orientation_feat) if pr.use_orientation else None,
-                                                _ptr(a["loc6"]), _ptr(ll[0].weight), _ptr(ll[0].bias), _ptr(ll[1].weight),
-                                                _ptr(ll[1].bias), ctypes.c_float(ll[1].eps), _ptr(a["pos"]), _ptr(a["sa"]),
-                                                _ptr(a["sta"]), _ptr(a["xin0"]), None if hyb else _vp(xp.data_ptr()), st)
-                _lib.check(rc, "msr3d_anchor_front_fwd")
-            else:
-                self._multi(front)
-                le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
-                # positional term + the layer input (tokens + positional term + the two constant rows) and its planes: one
-                # launch (the MSR3D_PRO_ADD rows launch of rounds 3-5 rides in it)
-                rc = lib.msr3d_pos_embed_tokens_fwd(
-                    M, L, KF, _ptr(a["ff"]), _ptr(a["loc6"]), _ptr(le[0].weight), _ptr(le[0].bias), _ptr(le[1].weight),
-                    _ptr(le[1].bias), ctypes.c_float(le[1].eps), _ptr(se[0].weight), _ptr(se[0].bias), _ptr(se[1].weight),
-                    _ptr(se[1].bias), ctypes.c_float(se[1].eps), _ptr(a["pos"]), _ptr(a["sa"]), _ptr(a["sta"]), _ptr(a["sb"]),
-                    _ptr(a["stb"]), _ptr(a["x0"]), _ptr(pr.object_type_embedding.weight),
-                    _ptr(pr.object_orientation_feat) if pr.use_orientation else None, _ptr(a["xin0"]),
-                    None if hyb else _vp(xp.data_ptr()), st)
-                _lib.check(rc, "msr3d_pos_embed_tokens_fwd")
+                self._step_begin()
+                if _PACK_FORK:
+                    if self._pack_stream is None:
+                        self._pack_stream = torch.cuda.Stream(device=dev)
+                    side = self._pack_stream
+                    side.wait_stream(torch.cuda.current_stream(dev))
+                    with torch.cuda.stream(side):
+                        pk.launch(_lib.current_stream_ptr(dev))
+                    join = side
+                else:
+                    pk.launch(st)
+            # (the positional launch also writes xin0 and, a scene being a block, the first block's planes: the
+            # MSR3D_PRO_ADD rows launch of rounds 3-5 rides in it)
+            self._front(e2, None if hyb else xp, tokens=True)
             for i, layer in enumerate(layers):
                 sa = layer.self_attn
                 bv = sa._packed[1]
                 p_attn, p1, p2, p_ffn = self.ps[i]
                 s_attn, s_1, s_2, s_ffn = self.salts[i]
-                if i == 0:
-                    pass        # (msr3d_pos_embed_tokens_fwd / msr3d_anchor_front_fwd wrote xin0 and its planes)
-                else:           # previous layer's closing norm (+ the positional term)
-                    prev = layers[i - 1]
-                    rows(st, M=M, L=Lt, pro=PRO["ln"], part=part, nslab=nff, part_stride=MD, a0_bias=prev.linear2.bias,
-                         sum_out=a[f"ffn{i-1}"], a1=a[f"t{i-1}"], a2=a["pos"] if same_all else None,
-                         g1=prev.norm2.weight, b1=prev.norm2.bias, eps1=prev.norm2.eps, p1=self.ps[i - 1][2],
-                         salt1=self.salts[i - 1][2], seed=seed, o0=a[f"s3_{i-1}"], ost1=a[f"st3_{i-1}"],
-                         o1=a[f"xin{i}"], xp=None if hyb else xp)
+                if i > 0:       # previous layer's closing norm (+ the positional term)
+                    close(i - 1, a[f"xin{i}"], a2=a["pos"] if same_all else None, xp=None if hyb else xp)
                 if join is not None:        # the packs are needed from here on
                     torch.cuda.current_stream(dev).wait_stream(join)
                     join = None
@@ -467,12 +525,7 @@ class PrompterSchedule:
                     wv = sa._packed[0]
                     self._strip(M=M, N=W, pro=PRO["plain"], epi=EPI["bias"], b_kc=1, a0=a[f"xin{i}"], W=wv, ldw=D, bias=bv,
                                 C=a[f"qkvc{i}"], ldc=W)
-                    q = a[f"qkvc{i}"]
-                    base, fs = q.data_ptr(), 4
-                    rc = lib.msr3d_spatial_attn_fwd(B, L, H, D // H, 5, _vp(base), _vp(base + D * fs), _vp(base + 2 * D * fs),
-                                                    W, _vp(base + 3 * D * fs), W, _ptr(a["pw"]), _ptr(self.pad),
-                                                    _ptr(a[f"ctx{i}"]), _ptr(a[f"probs{i}"]), hipops.attention_mma(False, training=True), st)
-                    _lib.check(rc, "msr3d_spatial_attn_fwd")
+                    self._attention_fwd(i)
                     self._strip(M=M, N=D, pro=PRO["plain"], epi=EPI["bias"], b_kc=1, a0=a[f"ctx{i}"], W=sa.fc.weight,
                                 ldw=D, bias=sa.fc.bias, C=a[f"fcacc{i}"], ldc=D)
                     rows(st, M=M, L=Lt, pro=PRO["ln2"], a0=a[f"fcacc{i}"], nslab=0, a1=a[f"xin{i}"],
@@ -492,17 +545,11 @@ class PrompterSchedule:
                 blk(st, kind=BLK["ffn_fwd"], B=Bt, L=Lt, xp=xp, w1=pk.bufs[f"w1_{i}"], w1_bytes=pk.nbytes(f"w1_{i}"),
                     bias1=layer.linear1.bias, w2=pk.bufs[f"w2_{i}"], w2_bytes=pk.nbytes(f"w2_{i}"), part=part,
                     part_stride=MD, pre=a[f"pre{i}"], h=a[f"h{i}"], ff=FF, p_drop=p_ffn, salt=s_ffn, seed=seed)
-            last = layers[-1]
-            tail = dict(M=M, L=Lt, pro=PRO["ln"], part=part, nslab=nff, part_stride=MD, a0_bias=last.linear2.bias,
-                        sum_out=a[f"ffn{nl-1}"], a1=a[f"t{nl-1}"], g1=last.norm2.weight, b1=last.norm2.bias,
-                        eps1=last.norm2.eps, p1=self.ps[-1][2], salt1=self.salts[-1][2], seed=seed,
-                        o0=a[f"s3_{nl-1}"], ost1=a[f"st3_{nl-1}"], o1=a["tok"])
+            close(len(layers) - 1, a["tok"], xp=xp if self.llm_blocks else None)
             if self.llm_blocks:
-                rows(st, xp=xp, **tail)
                 blk(st, kind=BLK["linear"], B=Bt, L=Lt, xp=xp, w1=pk.bufs["llm"], w1_bytes=pk.nbytes("llm"),
                     bias1=m.llm_proj.bias, C=a["scene"], ldc=E, N=E)
             else:
-                rows(st, **tail)
                 self._strip(M=M, N=E, pro=PRO["plain"], epi=EPI["bias"], b_kc=1, a0=a["tok"], W=m.llm_proj.weight,
                             ldw=D, bias=m.llm_proj.bias, C=a["scene"], ldc=E)
         return a["tok"].view(B, L, D), a["scene"].view(B, L, E)
@@ -511,13 +558,11 @@ class PrompterSchedule:
         """backward  d tok partials = d scene W_llm | 3 x [rows | feed-forward block bwd | rows | attention block
                      bwd] | rows (sum) | pos-bwd | ALL weight gradients in one launch"""
         pr, m, a, dm = self.pr, self.model, self.arena, self.dims
-        B, L, M, D, W, H, FF, E, KF, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E", "KF", "KE", "nl"))
+        B, L, M, D, W, H, FF, E, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E", "KE", "nl"))
         dev = a.buf.device
-        lib = self.lib
         self.stream = st = _lib.current_stream_ptr(dev)
         seed = hipops.seed_word(dev)
         layers = list(pr.spatial_encoder)
-        same_all = pr.cfg.spatial_encoder.obj_loc_encoding == "same_all"
         pk, wg, xp, part, MD = self.packs, self.wgrad, self.xp, a["part"], M * D
         hyb = self.hybrid
         Bt, Lt, RT = (self.tiles, 64, M) if hyb else (B, L, 0)
@@ -574,14 +619,8 @@ class PrompterSchedule:
                     wv = sa._packed[0]
                     self._strip(M=M, N=D, pro=PRO["plain"], epi=EPI["bias"], b_kc=0, a0=a[f"d_fc{i}"], W=sa.fc.weight, ldw=D,
                                 C=a["d_ctx"], ldc=D)
-                    q, gq = a[f"qkvc{i}"], a[f"d_qkvc{i}"]
-                    base, gb, fs = q.data_ptr(), gq.data_ptr(), 4
-                    rc = lib.msr3d_spatial_attn_bwd(B, L, H, D // H, 5, _vp(base), _vp(base + D * fs), _vp(base + 2 * D * fs),
-                                                    W, _vp(base + 3 * D * fs), W, _ptr(a["pw"]), _ptr(self.pad),
-                                                    _ptr(a[f"probs{i}"]), _ptr(a["d_ctx"]), _vp(gb), _vp(gb + D * fs),
-                                                    _vp(gb + 2 * D * fs), W, _vp(gb + 3 * D * fs), W,
-                                                    hipops.attention_mma(True), st)
-                    _lib.check(rc, "msr3d_spatial_attn_bwd")
+                    gq = a[f"d_qkvc{i}"]
+                    self._attention_bwd(i, gq)
                     self._multi([dict(a_kc=1, b_kc=0, M=M, N=D, K=W, A=gq, lda=W, B=wv, ldb=D, C=a[f"d_xin{i}"], ldc=D,
                                       beta=1.0)])
                     src = dict(a0=a[f"d_xin{i}"])
@@ -593,33 +632,13 @@ class PrompterSchedule:
                         probs=a[f"probs{i}"], H=H)
                     src = dict(part=part, nslab=H, part_stride=MD, extra=a["res"])
             rows(st, M=M, L=Lt, pro=PRO["plain"], sum_out=a["d_xacc0"], **src)     # d_xin0, whole
-            more = same_all and nl > 1
-            if self.anchor:
-                ll = pr.loc_layers[0]
-                tg = pr.object_type_embedding.weight.grad
-                rc = lib.msr3d_anchor_front_bwd(
-                    B, L, _ptr(a["d_xacc0"]), _ptr(a["d_xacc1"]) if more else None,
-                    _ptr(a["d_xacc2"]) if (more and nl > 2) else None, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(ll[1].weight),
-                    _ptr(a["d_la"]), _ptr(ll[1].weight.grad), _ptr(ll[1].bias.grad), _ptr(tg),
-                    _ptr(pr.object_orientation_feat.grad) if pr.use_orientation else None,
-                    _ptr(pr.obj_linear_projection.bias.grad), _ptr(tg, D), _ptr(pr.anchor_feat.grad), st)
-                _lib.check(rc, "msr3d_anchor_front_bwd")
-            else:
-                le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
-                rc = lib.msr3d_pos_embed_bwd(
-                    M, _ptr(a["d_xacc0"]), _ptr(a["d_xacc1"]) if more else None,
-                    _ptr(a["d_xacc2"]) if (more and nl > 2) else None, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(le[1].weight),
-                    _ptr(a["sb"]), _ptr(a["stb"]), _ptr(se[1].weight), _ptr(a["d_la"]), _ptr(a["d_lb"]),
-                    _ptr(le[1].weight.grad), _ptr(le[1].bias.grad), _ptr(se[1].weight.grad), _ptr(se[1].bias.grad),
-                    _ptr(pr.object_type_embedding.weight.grad),
-                    _ptr(pr.object_orientation_feat.grad) if pr.use_orientation else None, st)
-                _lib.check(rc, "msr3d_pos_embed_bwd")
+            self._front_bwd("d_xacc")
             wg.set_ptr(self.wg_proj, "x", self.saved_embeds.data_ptr())
             if _MERGE:
                 # every weight gradient + (as extra workgroups) the ordered LayerNorm-gradient column sums: one launch
                 wg.launch(st, colsum=(len(layers) * 6, self._ln_jobs(layers)))
             else:
-                _lib.check(lib.msr3d_colsum_partials(len(layers) * 6, _ptr(self._ln_jobs(layers)), st), "msr3d_colsum_partials")
+                _lib.call("msr3d_colsum_partials", len(layers) * 6, _ptr(self._ln_jobs(layers)), st)
                 wg.launch(st)
             if self.need_d_embeds:     # unfrozen object encoder: d obj_embeds = d_xin0 W_proj
                 lpj = pr.obj_linear_projection
@@ -645,29 +664,10 @@ class PrompterSchedule:
 
     # ------------------------------------------------------------------ launch helpers
     def _strip(self, **kw):
-        s = StripGemm()
-        for k, v in kw.items():
-            if isinstance(v, torch.Tensor):
-                v = v.data_ptr()
-            elif isinstance(v, _vp):
-                v = v.value
-            setattr(s, k, v if v is not None else 0)
-        rc = self.lib.msr3d_strip_gemm_f32(ctypes.byref(s), self.stream)
-        if rc:
-            fields = ", ".join(f"{n}={getattr(s, n)!r}" for n, _ in s._fields_ if getattr(s, n))
-            _lib.check(rc, f"msr3d_strip_gemm_f32({fields})")
+        _lib.launch("msr3d_strip_gemm_f32", _lib.fill(StripGemm(), kw), self.stream)
 
     def _multi(self, probs):
-        arr = (GemmProblem * len(probs))()
-        for q, kw in zip(arr, probs):
-            for k, v in kw.items():
-                if isinstance(v, torch.Tensor):
-                    v = v.data_ptr()
-                elif isinstance(v, _vp):
-                    v = v.value
-                setattr(q, k, v if v is not None else 0)
-        rc = self.lib.msr3d_gemm_multi_f32(len(probs), arr, self.stream)
-        _lib.check(rc, "msr3d_gemm_multi_f32")
+        _lib.launch("msr3d_gemm_multi_f32", _lib.fill((GemmProblem * len(probs))(), probs), self.stream)
 
     @staticmethod
     def _dw(dy, n_out, x, k_in, m_tok, dw, db):
@@ -689,29 +689,23 @@ class PrompterSchedule:
         loc = d["obj_locs"].contiguous()
         valid = d["obj_masks"].contiguous().view(torch.uint8)
         al, ao = d["anchor_locs"].contiguous(), d["anchor_orientation"].contiguous()
-        lib = _lib.load()
         if self.anchor:
             # the agent's row in front of every scene's (position + the constant anchor_size, always valid:
             # ose3d_situation.py:336-345) and its orientation as Fourier rows for the orientation encoder (:346-349): the
             # same one launch
             pr = self.pr
             with torch.cuda.device(dev):
-                rc = lib.msr3d_scene_prologue_agent(B, L, _ptr(loc), _ptr(valid), _ptr(al), _ptr(ao), _ptr(pr.anchor_size),
-                                                    _ptr(self.freqs), 10, ctypes.c_float(1e-10), _ptr(a["pw"]), _ptr(a["ff"]),
-                                                    _ptr(a["loc6"]), _ptr(self.pad), _ptr(self.valid),
-                                                    _ptr(a["qf"]) if pr.use_orientation else None,
-                                                    _ptr(anchor_out[0]) if anchor_out else None,
-                                                    _ptr(anchor_out[1]) if anchor_out else None,
-                                                    _lib.current_stream_ptr(dev))
-            _lib.check(rc, "msr3d_scene_prologue_agent")
+                _lib.call("msr3d_scene_prologue_agent", B, L, _ptr(loc), _ptr(valid), _ptr(al), _ptr(ao), _ptr(pr.anchor_size),
+                          _ptr(self.freqs), 10, ctypes.c_float(1e-10), _ptr(a["pw"]), _ptr(a["ff"]), _ptr(a["loc6"]),
+                          _ptr(self.pad), _ptr(self.valid), _ptr(a["qf"]) if pr.use_orientation else None,
+                          _ptr(anchor_out[0]) if anchor_out else None, _ptr(anchor_out[1]) if anchor_out else None,
+                          _lib.current_stream_ptr(dev))
             return
         with torch.cuda.device(dev):
-            rc = lib.msr3d_scene_prologue(B, L, _ptr(loc), _ptr(valid), _ptr(al), _ptr(ao), _ptr(self.freqs), 10, 1,
-                                          ctypes.c_float(1e-10), _ptr(a["pw"]), _ptr(a["ff"]), _ptr(a["loc6"]),
-                                          _ptr(self.pad), _ptr(self.valid),
-                                          _ptr(anchor_out[0]) if anchor_out else None,
-                                          _ptr(anchor_out[1]) if anchor_out else None, _lib.current_stream_ptr(dev))
-        _lib.check(rc, "msr3d_scene_prologue")
+            _lib.call("msr3d_scene_prologue", B, L, _ptr(loc), _ptr(valid), _ptr(al), _ptr(ao), _ptr(self.freqs), 10, 1,
+                      ctypes.c_float(1e-10), _ptr(a["pw"]), _ptr(a["ff"]), _ptr(a["loc6"]), _ptr(self.pad), _ptr(self.valid),
+                      _ptr(anchor_out[0]) if anchor_out else None, _ptr(anchor_out[1]) if anchor_out else None,
+                      _lib.current_stream_ptr(dev))
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, embeds):
@@ -719,63 +713,25 @@ class PrompterSchedule:
         if self._ran_blocks:
             return self.forward_blocks(embeds)
         pr, m, a, dm = self.pr, self.model, self.arena, self.dims
-        B, L, M, D, W, H, FF, E, KF, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E", "KF", "KE", "nl"))
+        B, L, M, D, W, FF, E, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "FF", "E", "nl"))
         dev = embeds.device
-        self.lib = lib = _lib.load()
-        self.stream = st = _lib.current_stream_ptr(dev)
-        train = m.training
         seed = hipops.seed_word(dev)
+        e2 = self._begin(embeds)
         anchor = self.anchor
-        if anchor:
-            a["e61"].view(B, L, KE)[:, 1:].copy_(embeds.reshape(B, L - 1, KE))
-            e2 = a["e61"]
-        else:
-            e2 = embeds.reshape(M, KE)
-            e2 = e2 if e2.is_contiguous() else e2.contiguous()
-        self.saved_embeds = e2
         layers = list(pr.spatial_encoder)
-        self.salts = [[hipops._next_salt() for _ in range(4)] for _ in layers]
-        self.ps = []
-        for layer in layers:
-            sa = layer.self_attn
-            self.ps.append((float(sa.dropout.p) if train else 0.0, float(layer.dropout1.p) if train else 0.0,
-                            float(layer.dropout2.p) if train else 0.0, float(layer.dropout.p) if train else 0.0))
         same_all = pr.cfg.spatial_encoder.obj_loc_encoding == "same_all"
+
+        def close(i, out, **kw):        # layer i's closing norm as the prologue of the GEMM that reads `out`
+            self._strip(M=M, epi=EPI["bias"], b_kc=1, a0=a[f"ffn{i}"], **self._norm2(i, out), **kw)
         with torch.cuda.device(dev):
-            rc = lib.msr3d_step_begin(_ptr(a.buf), a.zero_floats, _ptr(seed) if self.bump_seed else None, st)
-            _lib.check(rc, "msr3d_step_begin")
-            lp = pr.obj_linear_projection
-            front = [dict(a_kc=1, b_kc=1, M=M, N=D, K=KE, A=e2, lda=KE, B=lp.weight, ldb=KE, C=a["x0"], ldc=D,
-                          bias=lp.bias, beta=1.0)]
-            if anchor:
-                if pr.use_orientation:
-                    oe = pr.orientation_encoder
-                    front.append(dict(a_kc=1, b_kc=1, M=B, N=D, K=oe.in_features, A=a["qf"], lda=oe.in_features, B=oe.weight,
-                                      ldb=oe.in_features, C=a["a_ori"], ldc=D, bias=oe.bias, beta=1.0))
-                self._multi(front)
-                ll = pr.loc_layers[0]
-                rc = lib.msr3d_anchor_front_fwd(B, L, _ptr(a["x0"]), _ptr(a["a_ori"]), _ptr(pr.anchor_feat),
-                                                _ptr(pr.object_type_embedding.weight),
-                                                _ptr(pr.object_orientation_feat) if pr.use_orientation else None,
-                                                _ptr(a["loc6"]), _ptr(ll[0].weight), _ptr(ll[0].bias), _ptr(ll[1].weight),
-                                                _ptr(ll[1].bias), ctypes.c_float(ll[1].eps), _ptr(a["pos"]), _ptr(a["sa"]),
-                                                _ptr(a["sta"]), _ptr(a["xin0"]), None, st)
-                _lib.check(rc, "msr3d_anchor_front_fwd")
-            else:
-                self._multi(front)
-                le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
-                rc = lib.msr3d_pos_embed_fwd(M, KF, _ptr(a["ff"]), _ptr(a["loc6"]), _ptr(le[0].weight), _ptr(le[0].bias),
-                                             _ptr(le[1].weight), _ptr(le[1].bias), ctypes.c_float(le[1].eps),
-                                             _ptr(se[0].weight), _ptr(se[0].bias), _ptr(se[1].weight), _ptr(se[1].bias),
-                                             ctypes.c_float(se[1].eps), _ptr(a["pos"]), _ptr(a["sa"]), _ptr(a["sta"]),
-                                             _ptr(a["sb"]), _ptr(a["stb"]), st)
-                _lib.check(rc, "msr3d_pos_embed_fwd")
+            self._step_begin()
+            self._front(e2, None, tokens=False)
             for i, layer in enumerate(layers):
                 sa = layer.self_attn
                 wv, bv = sa._packed[0], sa._packed[1]
                 p_attn, p1, p2, p_ffn = self.ps[i]
                 s_attn, s_1, s_2, s_ffn = self.salts[i]
-                if i == 0 and anchor:       # (msr3d_anchor_front_fwd wrote the layer input)
+                if i == 0 and anchor:       # (_front's agent-token launch wrote the layer input)
                     self._strip(M=M, N=W, pro=PRO["plain"], epi=EPI["bias"], b_kc=1, a0=a["xin0"], W=wv, ldw=D, bias=bv,
                                 C=a["qkvc0"], ldc=W)
                 elif i == 0:
@@ -784,18 +740,9 @@ class PrompterSchedule:
                                 b1=_ptr(pr.object_orientation_feat) if pr.use_orientation else None,
                                 o1=a["xin0"], W=wv, ldw=D, bias=bv, C=a["qkvc0"], ldc=W)
                 else:
-                    prev = layers[i - 1]
-                    self._strip(M=M, N=W, pro=PRO["ln"], epi=EPI["bias"], b_kc=1, a0=a[f"ffn{i-1}"], a1=a[f"t{i-1}"],
-                                a2=a["pos"] if same_all else None, g1=prev.norm2.weight, b1=prev.norm2.bias,
-                                eps1=prev.norm2.eps, p1=self.ps[i - 1][2], salt1=self.salts[i - 1][2], seed=seed,
-                                o0=a[f"s3_{i-1}"], ost1=a[f"st3_{i-1}"], o1=a[f"xin{i}"], W=wv, ldw=D, bias=bv,
-                                C=a[f"qkvc{i}"], ldc=W)
-                q = a[f"qkvc{i}"]
-                base, fs = q.data_ptr(), 4
-                rc = lib.msr3d_spatial_attn_fwd(B, L, H, D // H, 5, _vp(base), _vp(base + D * fs), _vp(base + 2 * D * fs),
-                                                W, _vp(base + 3 * D * fs), W, _ptr(a["pw"]), _ptr(self.pad),
-                                                _ptr(a[f"ctx{i}"]), _ptr(a[f"probs{i}"]), hipops.attention_mma(False, training=True), st)
-                _lib.check(rc, "msr3d_spatial_attn_fwd")
+                    close(i - 1, a[f"xin{i}"], a2=a["pos"] if same_all else None, N=W, W=wv, ldw=D, bias=bv,
+                          C=a[f"qkvc{i}"], ldc=W)
+                self._attention_fwd(i)
                 self._strip(M=M, N=D, pro=PRO["plain"], epi=EPI["bias"], b_kc=1, a0=a[f"ctx{i}"], W=sa.fc.weight,
                             ldw=D, bias=sa.fc.bias, C=a[f"fc{i}"], ldc=D)
                 self._strip(M=M, N=FF, pro=PRO["ln2"], epi=EPI["gelu"], b_kc=1, a0=a[f"fc{i}"], a1=a[f"xin{i}"],
@@ -806,24 +753,18 @@ class PrompterSchedule:
                             C=a[f"h{i}"], ldc=FF, Cpre=a[f"pre{i}"], p_drop=p_ffn, salt=s_ffn)
                 self._multi([dict(a_kc=1, b_kc=1, M=M, N=D, K=FF, A=a[f"h{i}"], lda=FF, B=layer.linear2.weight, ldb=FF,
                                   C=a[f"ffn{i}"], ldc=D, bias=layer.linear2.bias, beta=1.0)])
-            last = layers[-1]
-            self._strip(M=M, N=E, pro=PRO["ln"], epi=EPI["bias"], b_kc=1, a0=a[f"ffn{nl-1}"], a1=a[f"t{nl-1}"],
-                        g1=last.norm2.weight, b1=last.norm2.bias, eps1=last.norm2.eps, p1=self.ps[-1][2],
-                        salt1=self.salts[-1][2], seed=seed, o0=a[f"s3_{nl-1}"], ost1=a[f"st3_{nl-1}"], o1=a["tok"],
-                        W=m.llm_proj.weight, ldw=D, bias=m.llm_proj.bias, C=a["scene"], ldc=E)
+            close(nl - 1, a["tok"], N=E, W=m.llm_proj.weight, ldw=D, bias=m.llm_proj.bias, C=a["scene"], ldc=E)
         return a["tok"].view(B, L, D), a["scene"].view(B, L, E)
 
     def backward(self, g_scene, g_tok):
         if self._ran_blocks:
             return self.backward_blocks(g_scene, g_tok)
         pr, m, a, dm = self.pr, self.model, self.arena, self.dims
-        B, L, M, D, W, H, FF, E, KF, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "H", "FF", "E", "KF", "KE", "nl"))
+        B, L, M, D, W, FF, E, KF, KE, nl = (dm[k] for k in ("B", "L", "M", "D", "W", "FF", "E", "KF", "KE", "nl"))
         dev = a.buf.device
-        lib = self.lib
-        self.stream = st = _lib.current_stream_ptr(dev)
+        self.stream = _lib.current_stream_ptr(dev)
         seed = hipops.seed_word(dev)
         layers = list(pr.spatial_encoder)
-        same_all = pr.cfg.spatial_encoder.obj_loc_encoding == "same_all"
         with torch.cuda.device(dev):
             if g_tok is not None:            # a consumer of obj_tokens besides llm_proj
                 a["d_tok"].add_(g_tok.reshape(M, D))
@@ -858,31 +799,17 @@ class PrompterSchedule:
                             o0=a["d_fc"], o1=a[f"d_xin{i}"], dg1=sa.layer_norm.weight.grad, db1=sa.layer_norm.bias.grad,
                             dg2=layer.norm1.weight.grad, db2=layer.norm1.bias.grad, W=sa.fc.weight, ldw=D,
                             C=a["d_ctx"], ldc=D)
-                q, gq = a[f"qkvc{i}"], a["d_qkvc"]
-                base, gb, fs = q.data_ptr(), gq.data_ptr(), 4
-                rc = lib.msr3d_spatial_attn_bwd(B, L, H, D // H, 5, _vp(base), _vp(base + D * fs), _vp(base + 2 * D * fs),
-                                                W, _vp(base + 3 * D * fs), W, _ptr(a["pw"]), _ptr(self.pad),
-                                                _ptr(a[f"probs{i}"]), _ptr(a["d_ctx"]), _vp(gb), _vp(gb + D * fs),
-                                                _vp(gb + 2 * D * fs), W, _vp(gb + 3 * D * fs), W,
-                                                hipops.attention_mma(True), st)
-                _lib.check(rc, "msr3d_spatial_attn_bwd")
+                gq = a["d_qkvc"]
+                self._attention_bwd(i, gq)
                 self._multi([dict(a_kc=1, b_kc=0, M=M, N=D, K=W, A=gq, lda=W, B=wv, ldb=D, C=a[f"d_xin{i}"], ldc=D,
                                   beta=1.0),
                              self._dw(gq, W, a[f"xin{i}"], D, M, gwv, gbv),
                              self._dw(a["d_fc"], D, a[f"ctx{i}"], D, M, sa.fc.weight.grad, sa.fc.bias.grad)])
                 d_out = a[f"d_xin{i}"]
-            more = same_all and nl > 1
+            self._front_bwd("d_xin")
+            lp = pr.obj_linear_projection
             if self.anchor:
                 ll = pr.loc_layers[0]
-                tg = pr.object_type_embedding.weight.grad
-                lp = pr.obj_linear_projection
-                rc = lib.msr3d_anchor_front_bwd(
-                    B, L, _ptr(a["d_xin0"]), _ptr(a["d_xin1"]) if more else None,
-                    _ptr(a["d_xin2"]) if (more and nl > 2) else None, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(ll[1].weight),
-                    _ptr(a["d_la"]), _ptr(ll[1].weight.grad), _ptr(ll[1].bias.grad), _ptr(tg),
-                    _ptr(pr.object_orientation_feat.grad) if pr.use_orientation else None, _ptr(lp.bias.grad), _ptr(tg, D),
-                    _ptr(pr.anchor_feat.grad), st)
-                _lib.check(rc, "msr3d_anchor_front_bwd")
                 # loc_layers[0][0] (6 -> 256), the orientation encoder over the agent rows of d xin0 (row stride L * 256),
                 # the projection against the features with a zero row per agent (its bias gradient came from the launch above)
                 last = [dict(a_kc=0, b_kc=0, M=D, N=6, K=M, A=a["d_la"], lda=D, B=a["loc6"], ldb=6, C=ll[0].weight.grad, ldc=6,
@@ -899,15 +826,6 @@ class PrompterSchedule:
                     self.dp.mark_ready(p)
                 return
             le, se = pr.loc_embedding_encoder, pr.size_embedding_encoder
-            rc = lib.msr3d_pos_embed_bwd(
-                M, _ptr(a["d_xin0"]), _ptr(a["d_xin1"]) if more else None,
-                _ptr(a["d_xin2"]) if (more and nl > 2) else None, _ptr(a["sa"]), _ptr(a["sta"]), _ptr(le[1].weight),
-                _ptr(a["sb"]), _ptr(a["stb"]), _ptr(se[1].weight), _ptr(a["d_la"]), _ptr(a["d_lb"]),
-                _ptr(le[1].weight.grad), _ptr(le[1].bias.grad), _ptr(se[1].weight.grad), _ptr(se[1].bias.grad),
-                _ptr(pr.object_type_embedding.weight.grad),
-                _ptr(pr.object_orientation_feat.grad) if pr.use_orientation else None, st)
-            _lib.check(rc, "msr3d_pos_embed_bwd")
-            lp = pr.obj_linear_projection
             last = [self._dw(a["d_la"], D, a["ff"], KF, M, le[0].weight.grad, le[0].bias.grad),
                     dict(a_kc=0, b_kc=0, M=D, N=3, K=M, A=a["d_lb"], lda=D, B=_ptr(a["loc6"], 3), ldb=6,
                          C=se[0].weight.grad, ldc=3, beta=1.0, colsum=se[0].bias.grad),

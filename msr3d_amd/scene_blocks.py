@@ -99,14 +99,11 @@ class WeightPacks:
             self._pfx = torch.tensor(self._prefix, dtype=torch.int32).to(self.device)
         if begin is not None:
             z, n, seed = begin
-            rc = _lib.load().msr3d_split_pack_begin(len(self.jobs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                                    self.total_pieces, _vp(z.data_ptr()), n,
-                                                    _vp(seed.data_ptr()) if seed is not None else None, stream)
-            _lib.check(rc, "msr3d_split_pack_begin")
+            _lib.call("msr3d_split_pack_begin", len(self.jobs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
+                      self.total_pieces, _vp(z.data_ptr()), n, _vp(seed.data_ptr()) if seed is not None else None, stream)
             return
-        rc = _lib.load().msr3d_split_pack(len(self.jobs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                          self.total_pieces, stream)
-        _lib.check(rc, "msr3d_split_pack")
+        _lib.call("msr3d_split_pack", len(self.jobs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
+                  self.total_pieces, stream)
 
 
 def head_segments(h, dh=32, d=256, sd1=6):
@@ -348,12 +345,10 @@ class WgradTable:
                     T = max(self.prefix[-1], slots)
                     self._ws = torch.empty(T * HALF_SLOT_FLOATS, dtype=torch.float32, device=self.device)
                     self._sync = torch.zeros(2 * T, dtype=torch.int32, device=self.device)
-                rc = _klib().msr3d_wgrad_stream(len(self.probs), _vp(self._table.data_ptr()), n_pieces, _vp(pieces.data_ptr()),
-                                                _vp(first.data_ptr()), n_wgs, slots, _vp(plan[7].data_ptr()),
-                                                _vp(self._ws.data_ptr()) if slots else None,
-                                                self._ws.numel() if slots else 0,
-                                                _vp(colsum[1].data_ptr()) if colsum is not None else None, stream)
-                _lib.check(rc, "msr3d_wgrad_stream")
+                _lib.call("msr3d_wgrad_stream", len(self.probs), _vp(self._table.data_ptr()), n_pieces, _vp(pieces.data_ptr()),
+                          _vp(first.data_ptr()), n_wgs, slots, _vp(plan[7].data_ptr()),
+                          _vp(self._ws.data_ptr()) if slots else None, self._ws.numel() if slots else 0,
+                          _vp(colsum[1].data_ptr()) if colsum is not None else None, stream, lib=_klib())
                 return
         whole = self._whole_tiles() if self.mixed else self.prefix[-1]
         if whole < self.prefix[-1]:
@@ -368,47 +363,24 @@ class WgradTable:
                 self._ws = torch.empty(T * HALF_SLOT_FLOATS, dtype=torch.float32, device=self.device)
                 self._sync = torch.zeros(2 * T, dtype=torch.int32, device=self.device)
             nj, jt = (colsum[0], _vp(colsum[1].data_ptr())) if colsum is not None else (0, _vp(0))
-            rc = _klib().msr3d_wgrad_split_mixed(len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                                     self.prefix[-1], whole, nj, jt, _vp(self._ws.data_ptr()),
-                                                     self._ws.numel(), _vp(self._sync.data_ptr()), stream)
-            _lib.check(rc, "msr3d_wgrad_split_mixed")
+            _lib.call("msr3d_wgrad_split_mixed", len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
+                      self.prefix[-1], whole, nj, jt, _vp(self._ws.data_ptr()), self._ws.numel(),
+                      _vp(self._sync.data_ptr()), stream, lib=_klib())
             return
         if colsum is not None:
-            rc = _klib().msr3d_wgrad_split_colsum(len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                                      self.prefix[-1], colsum[0], _vp(colsum[1].data_ptr()), stream)
-            _lib.check(rc, "msr3d_wgrad_split_colsum")
+            _lib.call("msr3d_wgrad_split_colsum", len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
+                      self.prefix[-1], colsum[0], _vp(colsum[1].data_ptr()), stream, lib=_klib())
             return
-        rc = _klib().msr3d_wgrad_split(len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
-                                           self.prefix[-1], stream)
-        _lib.check(rc, "msr3d_wgrad_split")
+        _lib.call("msr3d_wgrad_split", len(self.probs), _vp(self._table.data_ptr()), _vp(self._pfx.data_ptr()),
+                  self.prefix[-1], stream, lib=_klib())
 
 
 def launch_block(stream, **kw):
-    s = SceneBlock()
-    for k, v in kw.items():
-        if isinstance(v, torch.Tensor):
-            v = v.data_ptr()
-        elif isinstance(v, _vp):
-            v = v.value
-        setattr(s, k, v if v is not None else 0)
-    rc = _klib().msr3d_scene_block(ctypes.byref(s), stream)
-    if rc:
-        fields = ", ".join(f"{n}={getattr(s, n)!r}" for n, _ in s._fields_ if getattr(s, n))
-        _lib.check(rc, f"msr3d_scene_block({fields})")
+    _lib.launch("msr3d_scene_block", _lib.fill(SceneBlock(), kw), stream, lib=_klib())
 
 
 def launch_rows(stream, **kw):
-    s = SceneRows()
-    for k, v in kw.items():
-        if isinstance(v, torch.Tensor):
-            v = v.data_ptr()
-        elif isinstance(v, _vp):
-            v = v.value
-        setattr(s, k, v if v is not None else 0)
-    rc = _lib.load().msr3d_scene_rows(ctypes.byref(s), stream)
-    if rc:
-        fields = ", ".join(f"{n}={getattr(s, n)!r}" for n, _ in s._fields_ if getattr(s, n))
-        _lib.check(rc, f"msr3d_scene_rows({fields})")
+    _lib.launch("msr3d_scene_rows", _lib.fill(SceneRows(), kw), stream)
 
 
 __all__ = ["BLK", "PRO", "WeightPacks", "WgradTable", "launch_block", "launch_rows", "head_segments", "PIECE"]

@@ -22,13 +22,7 @@ rows = []
 
 
 def launch_block(stream, **kw):
-    s = SceneBlock()
-    for k, v in kw.items():
-        if isinstance(v, torch.Tensor):
-            v = v.data_ptr()
-        elif isinstance(v, ctypes.c_void_p):
-            v = v.value
-        setattr(s, k, v if v is not None else 0)
+    s = _lib.fill(SceneBlock(), kw)
     torch.cuda.synchronize()
     rc = lib.msr3d_scene_block(ctypes.byref(s), stream)
     assert rc == 0, rc
