@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 37
+#define MSR3D_ABI_VERSION 38
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1107,6 +1107,27 @@ typedef struct {
   int r, K, N, pad_;
 } msr3d_lora_shadow_job_t;
 int msr3d_lora_shadows(int njobs, const msr3d_lora_shadow_job_t *jobs_device, msr3d_stream_t stream);
+
+/* The LoRA pairs of a whole stack MERGED into copies of their frozen weights, in ONE launch (ABI v38; csrc/lora_merge.hip;
+ * peft's merge_and_unload for the LoraConfig targets of model/msr3d/msr3d.py:103-112): per job
+ *   out[n][k] = bf16_rne( W[n][k] + scale * sum_r B[n][r] A[r][k] )
+ * W (N, K) bf16 dense; A (r, K), B (N, r) the fp32 MASTERS (not their bf16 images); out (N, K) bf16 with row stride ldo
+ * (columns K .. ldo - 1 are not touched).  The sum is fp32 (v_mfma_f32_16x16x4_f32: an fmaf chain over r in a fixed
+ * order), then ONE fmaf(scale, sum, W) and one rounding to bf16.  r = 16 or 32; K % 8 == 0, ldo >= K, ldo % 8 == 0;
+ * W, A, B, out 16-byte aligned; `out` must not overlap W (no merging in place).  `jobs_device`: the table in DEVICE
+ * memory, like msr3d_lora_shadows'.  Unlike the other entries this one synchronises `stream` once: it reads the table
+ * back to check it before anything is written through its pointers and to size the grid (a merge runs once per weight
+ * version, never inside a step; not capturable).  A bad job gives MSR3D_EINVAL and nothing is launched; njobs == 0
+ * returns 0.  Tiles of all jobs are dealt over one grid; no atomics: two runs give the same bits. */
+typedef struct {
+  const void *W;               /* (N, K) bf16 */
+  const float *A, *B;          /* (r, K), (N, r) fp32 */
+  void *out; int ldo;          /* (N, K) bf16, row stride ldo */
+  int r, N, K;
+  float scale;
+  int pad_;
+} msr3d_lora_merge_job_t;
+int msr3d_lora_merge(int njobs, const msr3d_lora_merge_job_t *jobs_device, msr3d_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * KV-cached decoding of the LoRA-Llama stack (csrc/llm_decode.hip; msr3d_amd/llm/generate.py): what transformers'

@@ -64,6 +64,12 @@ class LoraShadowJob(ctypes.Structure):
                 ("r", _c_int), ("K", _c_int), ("N", _c_int), ("pad_", _c_int)]
 
 
+class LoraMergeJob(ctypes.Structure):
+    """msr3d_lora_merge_job_t (include/msr3d_hip.h)."""
+    _fields_ = [("W", _ptr), ("A", _ptr), ("B", _ptr), ("out", _ptr), ("ldo", _c_int), ("r", _c_int), ("N", _c_int),
+                ("K", _c_int), ("scale", _c_float), ("pad_", _c_int)]
+
+
 class SceneBlock(ctypes.Structure):
     """msr3d_scene_block_t (include/msr3d_hip.h)."""
     _fields_ = [("kind", _c_int), ("B", _c_int), ("L", _c_int), ("xp", _ptr), ("a0", _ptr), ("lda0", _c_int),
@@ -153,6 +159,7 @@ _SIGNATURES = {
     "msr3d_colsum_partials": [_c_int, _ptr, _ptr],
     "msr3d_lora_grad_pair": [_c_int, _c_int, _c_int, ctypes.POINTER(LoraGradJob), _c_float, _c_int, _ptr],
     "msr3d_lora_shadows": [_c_int, _ptr, _ptr],
+    "msr3d_lora_merge": [_c_int, _ptr, _ptr],
     "msr3d_bf16_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, ctypes.POINTER(SkinnyJob),
                                   _c_int, _ptr],
     "msr3d_bf16_skinny_lowrank_wide": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int,
@@ -279,7 +286,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 37       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 38       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def _check_abi(lib, path, may_lack_version=False):

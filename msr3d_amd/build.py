@@ -45,6 +45,7 @@ SOURCES = [
     ("seq_ce.hip", []),
     ("lora_linear.hip", []),
     ("lora_fp8.hip", []),
+    ("lora_merge.hip", []),
     ("llm_layer.hip", []),
     ("llm_attn.hip", []),
     ("llm_decode.hip", []),

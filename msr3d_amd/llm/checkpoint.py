@@ -100,12 +100,16 @@ def load_hf_state_dict(stack, state_dict, embed_out=None, strict=True):
     return unused
 
 
-def hf_state_dict(stack, embed=None):
-    """`stack` under Hugging Face LlamaForCausalLM keys (frozen weights only; bf16)."""
+def hf_state_dict(stack, embed=None, merged=False):
+    """`stack` under Hugging Face LlamaForCausalLM keys (frozen weights only; bf16).
+    merged: the projection weights are the merged planes bf16(W + s B A) of `stack.merged_weights()` (peft's
+    merge_and_unload): a plain LlamaForCausalLM checkpoint that computes the adapted model and needs no peft."""
     sd = {}
+    planes = stack.merged_weights() if merged else None
     for i, layer in enumerate(stack.layers):
         for n, grp in PROJ.items():
-            sd[f"model.layers.{i}.{grp}.{n}.weight"] = getattr(layer, grp)[n].weight.detach().clone()
+            mod = getattr(layer, grp)[n]
+            sd[f"model.layers.{i}.{grp}.{n}.weight"] = (planes[mod] if merged else mod.weight).detach().clone()
         sd[f"model.layers.{i}.input_layernorm.weight"] = layer.input_layernorm_weight.detach().clone()
         sd[f"model.layers.{i}.post_attention_layernorm.weight"] = layer.post_attention_layernorm_weight.detach().clone()
     sd["model.norm.weight"] = stack.norm_weight.detach().clone()

@@ -22,6 +22,8 @@ Four pieces:
                    q | k | v as ONE skinny launch, rotation + cache append, decode attention, o, RMSNorm, gate | up with the
                    SwiGLU epilogue, down; then the final norm and the head.  No host synchronisation inside `step`: lengths
                    and positions live in device memory.  Up to `max_rows` = 64 live rows (batch x beams).
+                   `lora="merged"`: the same walks on the stack's merged planes bf16(W + s B A) (one msr3d_lora_merge
+                   launch per weight version): every product is its R = 0 form and the r-row launches are gone.
 * `search`         greedy / beam search and sampling with transformers' semantics, written against the engine interface alone
                    (`reserve`, `prefill`, `expand`, `step`, and optionally `select` and `sample`), so it runs on the CPU with any
                    engine: that is how its logic is checked exactly against transformers.  A batch with more live rows
@@ -40,7 +42,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, current_stream_ptr, ptr
-from .decoder import ModuleProducts, _AttentionFn, decoder_stack, rope_tables
+from .decoder import MergedModuleProducts, ModuleProducts, _AttentionFn, decoder_stack, rope_tables
 from .lora import PAD_R, LoRALinear, _skinny, refresh_shadows
 
 
@@ -514,6 +516,47 @@ def _skinny_entry(M):
     return "msr3d_bf16_skinny_lowrank" if M <= 32 else "msr3d_bf16_skinny_lowrank_wide"
 
 
+def _skinny_project(h, mods, swiglu, planes):
+    """The projections `mods` of the same activations h (M, K) -> list of (M, N) bf16 (one tensor with swiglu), one launch
+    per input group.  planes None: W and the low-rank pair side by side (the r-row product s h A^T first, R = 64);
+    planes {module: bf16(W + s B A)}: the merged plane alone, R = 0 -- no r-row product, no low-rank activation."""
+    M, K = h.shape
+    dev = h.device
+    R = PAD_R if planes is None else 0
+    outs, calls = [None] * len(mods), {}
+    for j, m in enumerate(mods):
+        if planes is None:
+            m._sync_weight_t()
+        calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
+    if swiglu and len(calls) != 1:
+        # gate and up without a shared low-rank activation (modules moved to the device after construction leave
+        # their input group): two products and the stand-alone SwiGLU launch
+        gate, up = _skinny_project(h, mods, False, planes)
+        act = torch.empty_like(gate)
+        with torch.cuda.device(dev):
+            call("msr3d_swiglu_fwd", gate.numel(), ptr(gate), ptr(up), ptr(act), current_stream_ptr(dev))
+        return [act]
+    for js in calls.values():
+        u = None
+        if planes is None:
+            m0 = mods[js[0]]
+            a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
+            u = torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev)
+            _skinny(M, a_op.shape[0], K, h, a_op, u, PAD_R, m0.scaling, dev)
+        jobs = (_lib.SkinnyJob * len(js))()
+        for n, j in enumerate(js):
+            m = mods[j]
+            w = m.weight if planes is None else planes[m]
+            b2 = m._shadows(forward=True)[1].data_ptr() if planes is None else 0
+            if not (swiglu and n == 1):
+                outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
+            jobs[n] = _lib.SkinnyJob(w.data_ptr(), K, b2, R, outs[j].data_ptr() if outs[j] is not None else 0,
+                                     m.out_features, m.out_features)
+        with torch.cuda.device(dev):
+            call(_skinny_entry(M), M, K, R, ptr(h), K, ptr(u), R, len(js), jobs, int(swiglu), current_stream_ptr(dev))
+    return outs
+
+
 class SkinnyProducts:
     """decoder.ModuleProducts' operations for the M <= 64 live rows of one decode step: every product streams its weight
     once (msr3d_bf16_skinny_lowrank), members of one input group share the low-rank activation and ONE launch, gate | up
@@ -521,42 +564,11 @@ class SkinnyProducts:
 
     @staticmethod
     def project(h, mods, swiglu=False):
-        """The projections `mods` of the same activations h (M, K) -> list of (M, N) bf16 (one tensor with swiglu)."""
-        M, K = h.shape
-        dev = h.device
-        outs, calls = [None] * len(mods), {}
-        for j, m in enumerate(mods):
-            m._sync_weight_t()
-            calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
-        if swiglu and len(calls) != 1:
-            # gate and up without a shared low-rank activation (modules moved to the device after construction leave
-            # their input group): two products and the stand-alone SwiGLU launch
-            gate, up = SkinnyProducts.project(h, mods)
-            act = torch.empty_like(gate)
-            with torch.cuda.device(dev):
-                call("msr3d_swiglu_fwd", gate.numel(), ptr(gate), ptr(up), ptr(act), current_stream_ptr(dev))
-            return [act]
-        for js in calls.values():
-            m0 = mods[js[0]]
-            a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
-            u = torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev)
-            _skinny(M, a_op.shape[0], K, h, a_op, u, PAD_R, m0.scaling, dev)
-            jobs = (_lib.SkinnyJob * len(js))()
-            for n, j in enumerate(js):
-                m = mods[j]
-                b2 = m._shadows(forward=True)[1]
-                if not (swiglu and n == 1):
-                    outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
-                jobs[n] = _lib.SkinnyJob(m.weight.data_ptr(), K, b2.data_ptr(), PAD_R,
-                                         outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
-            with torch.cuda.device(dev):
-                call(_skinny_entry(M), M, K, PAD_R, ptr(h), K, ptr(u), PAD_R, len(js), jobs, int(swiglu),
-                     current_stream_ptr(dev))
-        return outs
+        return _skinny_project(h, mods, swiglu, None)
 
     @staticmethod
     def gated(h, gate, up):
-        return SkinnyProducts.project(h, (gate, up), swiglu=True)[0]
+        return _skinny_project(h, (gate, up), True, None)[0]
 
     @staticmethod
     def head(h, lm_head):
@@ -569,15 +581,38 @@ class SkinnyProducts:
         return logits
 
 
+class MergedSkinnyProducts:
+    """SkinnyProducts on merged weights (lora="merged"): the same launches -- the same input groups, gate | up with the
+    SwiGLU epilogue -- with R = 0 on the planes bf16(W + s B A) of LoRALlamaStack.merged_weights()."""
+
+    def __init__(self, planes):
+        self.planes = planes
+
+    def project(self, h, mods, swiglu=False):
+        return _skinny_project(h, mods, swiglu, self.planes)
+
+    def gated(self, h, gate, up):
+        return _skinny_project(h, (gate, up), True, self.planes)[0]
+
+    head = staticmethod(SkinnyProducts.head)
+
+
 # ----------------------------------------------------------------------------------------------------------- engine
 class CachedDecoder:
     """The decoding engine of a LoRALlamaStack (see the module docstring).  bf16 base weights only.  At most `max_rows`
-    live rows (batch x beams) per prefill; `search` splits a larger batch into groups of whole prompts."""
+    live rows (batch x beams) per prefill; `search` splits a larger batch into groups of whole prompts.
+    lora = "separate": the low-rank term beside the frozen weight (ModuleProducts / SkinnyProducts), the training
+    graph's arithmetic; "merged": every product on the stack's merged planes (MergedModuleProducts /
+    MergedSkinnyProducts; LoRALlamaStack.merged_weights states cost and staleness).  The strategy is chosen at every
+    prefill / score -- where the planes are rebuilt if a weight has been written since -- and kept for the steps that
+    follow."""
 
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
-    def __init__(self, stack):
-        self.stack = stack
+    def __init__(self, stack, lora="separate"):
+        if lora not in ("separate", "merged"):
+            raise ValueError(f"lora is 'separate' or 'merged', not {lora!r}")
+        self.stack, self.lora = stack, lora
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
         if any(m.base == "fp8" for m in self.mods):
             raise NotImplementedError("CachedDecoder: base='fp8' stacks are not supported (the decode products read the bf16 "
@@ -587,6 +622,16 @@ class CachedDecoder:
         l0 = stack.layers[0]
         self.H, self.D, self.hidden = l0.num_heads, l0.head_dim, l0.hidden_size
         self.cache, self._plan, self._tables = None, (1, 256), None
+        self._wide, self._skinny = ModuleProducts, SkinnyProducts
+
+    def _products(self):
+        """The strategies of this call, on current weights: bf16 images of the pairs, or the merged planes."""
+        if self.lora == "merged":
+            planes = self.stack.merged_weights()
+            self._wide, self._skinny = MergedModuleProducts(planes), MergedSkinnyProducts(planes)
+        else:
+            refresh_shadows(self.mods, False)
+        return self._wide
 
     def reserve(self, rows_per_prompt, new_tokens):
         self._plan = (int(rows_per_prompt), int(new_tokens))
@@ -625,12 +670,12 @@ class CachedDecoder:
         rows = max(t_max, Tp)
         cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
         self._tables = (cos, sin, rows)
-        refresh_shadows(self.mods, False)
+        products = self._products()
         first = slice(0, B * beams, beams)                     # a prompt's first row; expand() fills the others
 
         def attend(layer, i, h):              # q, k, v; the rotation by `pos`; the cache write; the full attention
             a = layer.self_attn
-            q, k, v = ModuleProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
+            q, k, v = products.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
             with torch.cuda.device(dev):
                 call("msr3d_rope_positions", B, Tp, H, D, ptr(q), ptr(k), ptr(pos), ptr(cos), ptr(sin), rows,
                      current_stream_ptr(dev))
@@ -639,7 +684,7 @@ class CachedDecoder:
             cache.v(i)[first, :T] = v[:, :T]
             return _AttentionFn.apply(q, k, v, keep)
 
-        logits = decoder_stack(st, x, attend, ModuleProducts, slice(T - 1, T))     # only the last position's are wanted
+        logits = decoder_stack(st, x, attend, products, slice(T - 1, T))           # only the last position's are wanted
         cache.len[first] = T
         cache.pos[first] = mask.sum(-1).to(torch.int32) if positions == "mask" else T
         cache.keep[first, :T] = keep[:, :T]
@@ -687,7 +732,7 @@ class CachedDecoder:
             rows = c.t_max + Sp
             cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
             self._tables = (cos, sin, rows)
-        refresh_shadows(self.mods, False)
+        products = self._products()
         scale = 1.0 / math.sqrt(D)
         V = st.lm_head.out_features
         out = torch.empty((B, C, S, V), dtype=torch.bfloat16, device=dev)
@@ -703,7 +748,7 @@ class CachedDecoder:
 
             def attend(layer, i, h):          # q, k, v; the rotation by `pos`; the suffix rows against the cached prefix
                 a = layer.self_attn
-                q, k, v = ModuleProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
+                q, k, v = products.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
                 ctx = torch.empty((N * Sp, HD), dtype=torch.bfloat16, device=dev)
                 with torch.cuda.device(dev):
                     s = current_stream_ptr(dev)
@@ -712,7 +757,7 @@ class CachedDecoder:
                          ptr(c.v(i)), ptr(c.len), ptr(c.keep), ptr(skeep), ctypes.c_float(scale), ptr(ctx), HD, s)
                 return ctx
 
-            out[:, c0:c0 + Cc] = decoder_stack(st, x, attend, ModuleProducts, wanted).view(B, Cc, S, V)
+            out[:, c0:c0 + Cc] = decoder_stack(st, x, attend, products, wanted).view(B, Cc, S, V)
         return out
 
     # -- one token ------------------------------------------------------------------------------------------------
@@ -732,10 +777,11 @@ class CachedDecoder:
         cos, sin, rows = self._tables
         scale = 1.0 / math.sqrt(D)
         ws = c.workspace
+        products = self._skinny
 
         def attend(layer, i, h):              # q | k | v in one launch; rotation + cache append; the decode attention
             a = layer.self_attn
-            q, k, v = SkinnyProducts.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
+            q, k, v = products.project(h, (a["q_proj"], a["k_proj"], a["v_proj"]))
             ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=dev)
             with torch.cuda.device(dev):
                 s = current_stream_ptr(dev)
@@ -745,7 +791,7 @@ class CachedDecoder:
                      ctypes.c_float(scale), ptr(ctx), HD, ptr(ws), ws.numel() if ws is not None else 0, s)
             return ctx
 
-        logits = decoder_stack(st, x, attend, SkinnyProducts)
+        logits = decoder_stack(st, x, attend, products)
         c.len.add_(1)
         c.pos.add_(1)
         return logits
@@ -813,14 +859,17 @@ class CachedDecoder:
 
 
 @torch.no_grad()
-def generate(stack, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
-    """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); search_kwargs:
-    everything `search` takes (do_sample, top_p, top_k, temperature, num_return_sequences, seed, draw among them)."""
-    return search(CachedDecoder(stack), _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
+def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", **search_kwargs):
+    """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); lora: the
+    engine's products, "separate" or "merged" (CachedDecoder); search_kwargs: everything `search` takes (do_sample, top_p,
+    top_k, temperature, num_return_sequences, seed, draw among them)."""
+    return search(CachedDecoder(stack, lora=lora), _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
 
 
 @torch.no_grad()
-def predict_answers(stack, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs):
-    """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder; rank_kwargs: num_ans_candidates, bos_id."""
-    return rank_answers(CachedDecoder(stack), _embed_fn(embed_tokens), inputs_embeds, attention_mask, answer_ids, answer_mask,
-                        **rank_kwargs)
+def predict_answers(stack, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
+                    **rank_kwargs):
+    """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder(lora=lora); rank_kwargs: num_ans_candidates,
+    bos_id."""
+    return rank_answers(CachedDecoder(stack, lora=lora), _embed_fn(embed_tokens), inputs_embeds, attention_mask, answer_ids,
+                        answer_mask, **rank_kwargs)

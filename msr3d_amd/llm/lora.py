@@ -155,6 +155,27 @@ def refresh_shadows(mods, capturing=False):
         m._shadow_key = "captured" if capturing else m._pair_key()
 
 
+def merge_pairs(mods, planes):
+    """planes[i] (N, K) bf16 = bf16(W + s B A) of mods[i] (LoRALinear, bf16 base), computed from the fp32 masters of A / B
+    -- peft's merge_and_unload -- for ALL of them in ONE launch (msr3d_lora_merge, csrc/lora_merge.hip).  The job table
+    is built per call: a merge runs once per weight version, and the entry reads the table back to check it."""
+    if not mods:
+        return
+    dev = mods[0].weight.device
+    jobs = []
+    for m, out in zip(mods, planes):
+        if m.base != "bf16":
+            raise NotImplementedError("merge_pairs: base='fp8' modules are not merged (their products read e4m3 weights)")
+        if out.shape != m.weight.shape or out.dtype != torch.bfloat16 or out.device != dev or not out.is_contiguous():
+            raise ValueError("merge_pairs: a plane must be a contiguous bf16 tensor of its weight's shape and device")
+        jobs.append(_lib.LoraMergeJob(m.weight.data_ptr(), m.lora_A.weight.data_ptr(), m.lora_B.weight.data_ptr(),
+                                      out.data_ptr(), m.in_features, m.r, m.out_features, m.in_features, m.scaling, 0))
+    arr = (_lib.LoraMergeJob * len(jobs))(*jobs)
+    tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    with torch.cuda.device(dev):
+        call("msr3d_lora_merge", len(jobs), ptr(tab), current_stream_ptr(dev))
+
+
 class _LoRAFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, lora_A, lora_B, mod):
@@ -319,6 +340,7 @@ class LoRALinear(nn.Module):
         self._shadow, self._shadow_key = None, None
         self._fresh_in_capture = False    # set by LoRALlamaStack around a captured forward (its one refresh launch)
         self._group, self._u_col = None, 0    # group_inputs(): modules reading the same tensor share one r-row product
+        self._invalidations = 0               # invalidate_shadows() calls: part of the key of a stack's merged planes
 
     def _shadows(self, forward=False):
         """Zero-padded bf16 copies of A / B in the four orientations forward and backward read
@@ -343,8 +365,15 @@ class LoRALinear(nn.Module):
 
     def invalidate_shadows(self):
         """Force the bf16 copies of A / B to be rebuilt at the next forward / backward (for writers that changed
-        the parameters without going through autograd or FlatAdamW.mark_written)."""
+        the parameters without going through autograd or FlatAdamW.mark_written); a stack's merged planes
+        (LoRALlamaStack.merged_weights) are rebuilt as well."""
         self._shadow_key = None
+        self._invalidations += 1
+
+    def _merge_key(self):
+        """What a merged plane bf16(W + s B A) was built from: the pair, the base weight, the explicit invalidations."""
+        w = self.weight
+        return (self._pair_key(), w._version, w.data_ptr(), self._invalidations)
 
     def _sync_weight_t(self):
         """weight_t is a cache of weight^T (non-persistent): rebuilt whenever `weight` has been written --

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from .. import _lib
 from .decoder import LoRALlamaDecoderLayer, ModuleProducts, causal_attention, decoder_stack
-from .lora import LoRALinear, _gemm as _lora_gemm, refresh_shadows
+from .lora import LoRALinear, _gemm as _lora_gemm, merge_pairs, refresh_shadows
 from .losses import seq_mean_cross_entropy
 
 
@@ -107,6 +107,7 @@ class LoRALlamaStack(nn.Module):
         self.lm_head = FrozenLinear(hidden_size, vocab_size, device=device)
         self.eps = rms_eps
         self._lora_mods = None
+        self._merged = None           # (key, {module: plane}) of merged_weights()
 
     def lora_parameters(self):
         return [p for p in self.parameters() if p.requires_grad]
@@ -115,6 +116,36 @@ class LoRALlamaStack(nn.Module):
         if self._lora_mods is None:
             self._lora_mods = [m for m in self.modules() if isinstance(m, LoRALinear)]
         return self._lora_mods
+
+    def merged_weights(self):
+        """-> {LoRALinear: plane (N, K) bf16 = bf16(W + s B A)} for every projection of the stack: peft's
+        merge_and_unload, from the fp32 masters of A / B, which `generate` / `predict_answers` with lora="merged" and
+        checkpoint.hf_state_dict(merged=True) read.  The planes are allocated once and live on the stack -- an engine is
+        built per call -- and are rebuilt, all in ONE launch (msr3d_lora_merge), only when stale: when any pair's
+        `_pair_key()` or any base weight's (version, data_ptr) differs from what they were built from, or a module's
+        `invalidate_shadows()` has been called (FlatAdamW.mark_written moves the pair key).  A call on fresh planes costs
+        that key comparison and nothing else.
+        MEMORY: one more copy of the seven projections of every layer -- 13 GB for a 7B model -- until
+        `release_merged()`.  base="fp8" stacks are refused."""
+        mods = self._pairs()
+        if any(m.base == "fp8" for m in mods):
+            raise NotImplementedError("LoRALlamaStack.merged_weights: base='fp8' stacks are not supported (their products "
+                                      "read e4m3 weights; merged e4m3 decoding is not implemented)")
+        key = tuple(m._merge_key() for m in mods)
+        if self._merged is not None and self._merged[0] == key:
+            return self._merged[1]
+        planes = self._merged[1] if self._merged is not None else {}
+        if any(m not in planes or planes[m].device != m.weight.device for m in mods):
+            planes = {m: torch.empty_like(m.weight) for m in mods}
+        self._merged = None                                    # (a failed merge leaves no half-built planes behind)
+        with torch.no_grad():
+            merge_pairs(mods, [planes[m] for m in mods])
+        self._merged = (key, planes)
+        return planes
+
+    def release_merged(self):
+        """Free the merged planes (the next lora="merged" call builds them again)."""
+        self._merged = None
 
     def logits(self, inputs_embeds, attention_mask=None, from_position=0):
         """from_position = p: only the logits of positions p .. T-1 (B, T - p, V) -- the attention of every layer still runs
@@ -138,7 +169,7 @@ class LoRALlamaStack(nn.Module):
             for m in mods:
                 m._fresh_in_capture = False
 
-    def generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs):
+    def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", **search_kwargs):
         """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
         -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
         (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
@@ -146,16 +177,22 @@ class LoRALlamaStack(nn.Module):
         temperature, num_return_sequences, seed, draw (`search` states them: nucleus / top-k sampling and beam sampling
         with transformers' semantics, drawn by msr3d_decode_sample from counter noise -- the same seed, the same tokens).
         Any batch: up to 64 live rows (B x max(num_beams, num_return_sequences)) decode in one pass, more in groups of
-        whole prompts one after another (the same tokens)."""
+        whole prompts one after another (the same tokens).
+        lora = "separate" (default): the low-rank term is computed beside the frozen weight, as in training;
+        lora = "merged": every product streams the merged plane bf16(W + s B A) of `merged_weights()` alone (no r-row
+        launches; one more copy of the projections in memory; the weights rounded once more, so other bits)."""
         from .generate import generate
-        return generate(self, inputs_embeds, attention_mask, embed_tokens, **search_kwargs)
+        return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, **search_kwargs)
 
-    def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs):
+    def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
+                        **rank_kwargs):
         """Closed-set answer ranking on one cached copy of every prompt (msr3d_amd/llm/generate.py::rank_answers) ->
         dict(answers_id (B,), topk_ids (B, C), loss (B, C) fp32, first_prob (B, A)).  answer_ids / answer_mask (A, S):
-        the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id."""
+        the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id; lora: as in
+        `generate`."""
         from .generate import predict_answers
-        return predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, **rank_kwargs)
+        return predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora=lora,
+                               **rank_kwargs)
 
     def forward(self, inputs_embeds, attention_mask=None, targets=None, supervised_from=None):
         """-> logits (B, T, V) bf16, or with `targets` (B, T) int64 (negative = not supervised) the per-sequence mean

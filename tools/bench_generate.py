@@ -7,16 +7,20 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
     python tools/bench_generate.py [--layers 4] [--repeats 20] [--rows 1,5,20,32,40,64] [--lengths 128,320,576]
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --profile 5x320      # per-kernel, own run
     python tools/bench_generate.py --sample      # the draw kernel beside the select kernel and a decode step
+    python tools/bench_generate.py --lora both   # + the step on merged weights (lora="merged"), alternating with the
+                                                 #   separate one; the merge launch; launches per step; the fresh-call cost
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from msr3d_amd import _lib  # noqa: E402
 from msr3d_amd.llm import LoRALlamaStack  # noqa: E402
 from msr3d_amd.llm.generate import CachedDecoder  # noqa: E402
 
@@ -51,6 +55,72 @@ def timed(fn, repeats, warmup=3):
         ts.append(e0.elapsed_time(e1) * 1e3)
     ts.sort()
     return {"median_us": round(statistics.median(ts), 1), "min_us": round(ts[0], 1), "max_us": round(ts[-1], 1)}
+
+
+def _stats(ts):
+    ts = sorted(ts)
+    return {"median_us": round(statistics.median(ts), 1), "min_us": round(ts[0], 1), "max_us": round(ts[-1], 1)}
+
+
+def timed_alternating(fns, repeats, warmup=3):
+    """Several callables timed in turn, repeat by repeat (what the machine does in between hits all of them alike)."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(repeats):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts[i].append(e0.elapsed_time(e1) * 1e3)
+    return [_stats(t) for t in ts]
+
+
+def library_launches(fn):
+    """The library entries one call of fn launches, by name (the binding's census brackets every launch)."""
+    sink = {}
+    _lib.set_timing_sink(sink, census=True)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_timing_sink(None)
+    return {k: len(v) for k, v in sorted(sink.items())}
+
+
+def merge_cell(net, repeats):
+    """The merge launch over every pair of the stack: events around the ENTRY on a table built beforehand (the entry reads
+    the table back before it launches) and around llm.lora.merge_pairs, which also builds and uploads the table; the bytes
+    -- 2 read + 2 written per element -- over the copy rate; a device copy of as many bytes; the host cost of a call on
+    fresh planes."""
+    from msr3d_amd.llm.lora import merge_pairs
+    planes = net.merged_weights()
+    mods = list(planes)
+    arr = (_lib.LoraMergeJob * len(mods))(*[
+        _lib.LoraMergeJob(m.weight.data_ptr(), m.lora_A.weight.data_ptr(), m.lora_B.weight.data_ptr(), planes[m].data_ptr(),
+                          m.in_features, m.r, m.out_features, m.in_features, m.scaling, 0) for m in mods])
+    tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).cuda()
+    dev = tab.device
+    entry, pairs = timed_alternating([
+        lambda: _lib.call("msr3d_lora_merge", len(mods), _lib.ptr(tab), _lib.current_stream_ptr(dev)),
+        lambda: merge_pairs(mods, [planes[m] for m in mods])], repeats)
+    nbytes = sum(4 * m.in_features * m.out_features for m in mods)
+    src = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    copy = timed(lambda: dst.copy_(src), repeats)
+    del src, dst
+    t0 = time.perf_counter()
+    for _ in range(200):
+        net.merged_weights()
+    fresh = (time.perf_counter() - t0) / 200 * 1e6
+    floor = nbytes / COPY_RATE * 1e6
+    return {"pairs": len(mods), "bytes": nbytes, "entry": entry, "merge_pairs": pairs, "device_copy_same_bytes": copy,
+            "floor_us": round(floor, 1), "floor_fraction": round(floor / entry["median_us"], 3),
+            "fresh_call_host_us": round(fresh, 1)}
 
 
 def step_bytes(layers, rows, length):
@@ -100,6 +170,8 @@ def main():
     ap.add_argument("--rows", default="1,5,20,32,40,64")
     ap.add_argument("--lengths", default="128,320,576")
     ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
+    ap.add_argument("--lora", default="separate", choices=("separate", "merged", "both"),
+                    help="the engine's products; both: the two steps timed in turn in one process")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
     if args.sample:
@@ -112,11 +184,13 @@ def main():
         grid = [tuple(int(v) for v in args.profile.split("x"))]
     out = {"bench": "generate", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
            "heads": HEADS, "inter": INTER, "vocab": VOCAB, "repeats": args.repeats, "copy_rate_TBps": COPY_RATE / 1e12,
-           "cells": []}
+           "lora": args.lora, "cells": []}
+    if args.lora != "separate" and not args.profile:
+        out["merge"] = merge_cell(net, args.repeats)
     for rows, length in grid:
         x = (torch.randn(1, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
         mask = torch.ones(1, length, dtype=torch.int64, device="cuda")
-        eng = CachedDecoder(net)
+        eng = CachedDecoder(net, lora="merged" if args.lora == "merged" else "separate")
         eng.reserve(rows, args.repeats + 8)
         prefill = None
         if not args.profile:
@@ -124,8 +198,23 @@ def main():
         eng.prefill(x, mask)
         eng.expand(rows)
         tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
-        cached = timed(lambda: eng.step(tok), args.repeats)
+        if args.lora == "both":
+            other = CachedDecoder(net, lora="merged")
+            other.reserve(rows, args.repeats + 8)
+            other.prefill(x, mask)
+            other.expand(rows)
+            cached, merged = timed_alternating([lambda: eng.step(tok), lambda: other.step(tok)], args.repeats)
+        else:
+            cached, merged = timed(lambda: eng.step(tok), args.repeats), None
         cell = {"rows": rows, "length": length, "prefill_1row": prefill, "step": cached}
+        if merged is not None:
+            cell["step_merged"] = merged
+            cell["merged_over_separate"] = round(merged["median_us"] / cached["median_us"], 3)
+            if "launches" not in out:
+                a, b = library_launches(lambda: eng.step(tok)), library_launches(lambda: other.step(tok))
+                out["launches"] = {"separate": sum(a.values()), "merged": sum(b.values()), "separate_by_entry": a,
+                                   "merged_by_entry": b, "torch_ops_per_step": 2}
+            del other
         floor = step_bytes(args.layers, rows, length) / COPY_RATE * 1e6
         cell["floor_us"] = round(floor, 1)
         cell["floor_fraction"] = round(floor / cached["median_us"], 3)
