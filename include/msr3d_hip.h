@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MSR3D_ABI_VERSION 38
+#define MSR3D_ABI_VERSION 39
 #define MSR3D_EINVAL (-22)
 
 typedef void *msr3d_stream_t; /* hipStream_t */
@@ -1160,6 +1160,18 @@ int msr3d_lora_merge(int njobs, const msr3d_lora_merge_job_t *jobs_device, msr3d
  *   key, or NULL; a row with no visible key gives 0.  D = 64 or 128.  A (row, head)'s keys are split over the four
  *   waves of a workgroup and, with a workspace, over msr3d_attn_decode_splits(N, H) workgroups whose partial
  *   (max, sum, out) a second launch merges in split order; workspace_floats >= N H splits (D + 2), or workspace NULL.
+ * msr3d_attn_decode_shared (ABI v39): msr3d_attn_decode for B prompts of G rows each (beams; row b G + g of q and out)
+ *   whose prompt keys are stored ONCE per prompt: logical key t of row (b, g) is slot t of k_prompt / v_prompt
+ *   (B, T, H, D) bf16 for t < T and slot t - T of the row's own k_tail / v_tail (B G, Ttail, H, D) otherwise.
+ *   L = T + clamp(tail_len[b] + len_add, 0, Ttail) keys, tail_len (B) int32 on the device: every row of a prompt has
+ *   the same length.  prompt_keep (B, T) bytes, 0 = padded key, or NULL; tail slots are always visible; a row with no
+ *   visible key gives 0.  T >= 1; Ttail == 0: the tail planes may be NULL.  A workgroup serves up to 8 rows of one
+ *   prompt and loads a prompt key once for all of them.  splits 0: the splits msr3d_attn_decode takes for B G rows
+ *   (msr3d_attn_decode_splits(B G, H) with a workspace, 1 without); 1 .. MSR3D_ATTN_DECODE_MAX_SPLITS: that many;
+ *   more than one needs workspace_floats >= B G H splits (D + 2).  For equal splits the output is BIT-IDENTICAL to
+ *   msr3d_attn_decode on the materialised (B G, T + Ttail, H, D) cache with len = T + tail_len: both kernels state the
+ *   per-key update, the lane-group butterfly, the wave merge and the split merge through the same device functions,
+ *   and walk a row's keys in the same order.  No atomics.
  * msr3d_kv_reorder: beam search's gather dst[p][n][t] = src[p][beam_idx[n]][t], t < len[beam_idx[n]], over all
  *   `planes` (layers x {k, v}) of a (planes, N, Tmax, row_elems) bf16 cache in one launch; src != dst (two buffers
  *   ping-ponged); len describes the SOURCE rows; row_elems % 8 == 0.
@@ -1213,6 +1225,10 @@ int msr3d_attn_decode_splits(int N, int H);
 int msr3d_attn_decode(int N, int Tmax, int H, int D, const void *q, int ldq, const void *k_cache, const void *v_cache,
                       const int *len, int len_add, const unsigned char *key_keep, float scale, void *out, int ldo,
                       float *workspace, long long workspace_floats, msr3d_stream_t stream);
+int msr3d_attn_decode_shared(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq, const void *k_prompt,
+                             const void *v_prompt, const unsigned char *prompt_keep, const void *k_tail, const void *v_tail,
+                             const int *tail_len, int len_add, float scale, void *out, int ldo, float *workspace,
+                             long long workspace_floats, int splits, msr3d_stream_t stream);
 int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src, void *dst, const int *beam_idx,
                      const int *len, msr3d_stream_t stream);
 int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,

@@ -170,6 +170,8 @@ _SIGNATURES = {
     "msr3d_attn_decode_splits": [_c_int, _c_int],
     "msr3d_attn_decode": [_c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _c_float, _ptr,
                           _c_int, _ptr, ctypes.c_longlong, _ptr],
+    "msr3d_attn_decode_shared": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                 _ptr, _c_int, _c_float, _ptr, _c_int, _ptr, ctypes.c_longlong, _c_int, _ptr],
     "msr3d_kv_reorder": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
     "msr3d_decode_select": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,
                             _c_int, _ptr, _ptr, _ptr],
@@ -286,7 +288,7 @@ def exported_symbols():
     return ["msr3d_abi_version", "msr3d_status_string", "msr3d_sqdist_contract", "msr3d_wgrad_form"] + list(_SIGNATURES)
 
 
-ABI_VERSION = 38       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
+ABI_VERSION = 39       # MSR3D_ABI_VERSION of include/msr3d_hip.h these signatures were written for
 
 
 def _check_abi(lib, path, may_lack_version=False):

@@ -7,6 +7,7 @@
 //     msr3d_rope_kv_append        rotate q, k by the row's own position, write k, v into cache slot len[n]
 //     msr3d_rope_positions        the prefill twin: (B, T, H, D) rotated by pos (B, T)
 //     msr3d_attn_decode           one query row per (row, head) against the row's cache: a stream over K and V
+//     msr3d_attn_decode_shared    the same bits with the prompt's keys stored once per prompt: up to 8 rows a workgroup
 //     msr3d_kv_reorder            beam search's cache gather, every layer in one launch
 //     msr3d_decode_select         logits processors + log-softmax + the row's top-k candidates
 //
@@ -294,6 +295,81 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(int n_items, int H,
 // S > 1 -- over the splits by attn_merge_kernel in split order.  exp2 throughout, the scale folded with log2 e.
 constexpr float kNegBig = -1.0e30f;
 
+// The arithmetic of a (row, head), stated once for attn_decode_kernel and attn_decode_shared_kernel -- the two give the
+// same bits because they call these four in the same order per row.  Every multiply-add is an explicit fmaf: left as
+// a * b + c * d, the compiler chooses per inlined copy which product it fuses (or none, where it packs two lanes), and
+// two kernels that share the expression still differ in the last bit.
+// One key (this lane's 16-byte pieces of K and V) into a lane group's online-softmax state.
+template <int LPK>
+__device__ __forceinline__ void attn_key_update(const float (&qf)[8], uint4 kv, uint4 vv, bool on, float &m, float &l,
+                                                float (&o)[8]) {
+  float kf[8], vf[8];
+  unpack8(kv, kf);
+  unpack8(vv, vf);
+  float sc = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) sc = fmaf(qf[e], kf[e], sc);
+#pragma unroll
+  for (int x = 1; x < LPK; x <<= 1) sc += __shfl_xor(sc, x);
+  if (on) {
+    const float mn = fmaxf(m, sc);
+    const float f = exp2f(m - mn), p = exp2f(sc - mn);
+    l = fmaf(l, f, p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = fmaf(o[e], f, p * vf[e]);
+    m = mn;
+  }
+}
+
+// the wave's lane groups (same dims, different keys): butterfly over the group index -- every lane of a dim ends with the
+// same value, in an order fixed by the lane numbers
+template <int LPK>
+__device__ __forceinline__ void attn_group_merge(int lane, float &m, float &l, float (&o)[8]) {
+#pragma unroll
+  for (int x = LPK; x < 64; x <<= 1) {
+    const float m2 = __shfl_xor(m, x), l2 = __shfl_xor(l, x);
+    const float mn = fmaxf(m, m2);
+    // (both factors from the lower and the upper partner in the same roles on both sides: a + b with a from the lower lane)
+    const bool low = (lane & x) == 0;
+    const float fa = exp2f((low ? m : m2) - mn), fb = exp2f((low ? m2 : m) - mn);
+    l = fmaf(low ? l : l2, fa, (low ? l2 : l) * fb);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float o2 = __shfl_xor(o[e], x);
+      o[e] = fmaf(low ? o[e] : o2, fa, (low ? o2 : o[e]) * fb);
+    }
+    m = mn;
+  }
+}
+
+// the four waves' states of dim d out of LDS, in wave order
+__device__ __forceinline__ void attn_wave_merge(const float *sm, const float *sl, const float *so, int ld_so, int d, float &mm,
+                                                float &ll, float &oo) {
+  mm = sm[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) mm = fmaxf(mm, sm[w]);
+  ll = 0.f, oo = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float f = exp2f(sm[w] - mm);
+    ll = fmaf(sl[w], f, ll);
+    oo = fmaf(so[w * ld_so + d], f, oo);
+  }
+}
+
+// dim d of (row n, head h): a split's partial state, or the output when there is one split
+template <int D>
+__device__ __forceinline__ void attn_store(int n, int h, int H, int s, int S, int d, float mm, float ll, float oo,
+                                           u16 *__restrict__ out, int ldo, float *__restrict__ part) {
+  if (part) {
+    float *pp = part + (((size_t)n * H + h) * S + s) * (D + 2);
+    if (d == 0) { pp[0] = mm; pp[1] = ll; }
+    pp[2 + d] = oo;
+  } else {
+    out[(size_t)n * ldo + (size_t)h * D + d] = f2bf(ll > 0.f ? oo / ll : 0.f);       // no visible key: 0
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const u16 *__restrict__ q, int ldq,
                                                           const u16 *__restrict__ kc, const u16 *__restrict__ vc,
@@ -329,42 +405,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const
       vv[u] = *reinterpret_cast<const uint4 *>(vc + off);
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float kf[8], vf[8];
-      unpack8(kv[u], kf);
-      unpack8(vv[u], vf);
-      float sc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sc += qf[e] * kf[e];
-#pragma unroll
-      for (int x = 1; x < LPK; x <<= 1) sc += __shfl_xor(sc, x);
-      if (on[u]) {
-        const float mn = fmaxf(m, sc);
-        const float f = exp2f(m - mn), p = exp2f(sc - mn);
-        l = l * f + p;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = o[e] * f + p * vf[e];
-        m = mn;
-      }
-    }
+    for (int u = 0; u < U; ++u) attn_key_update<LPK>(qf, kv[u], vv[u], on[u], m, l, o);
   }
-  // the wave's lane groups (same dims, different keys): butterfly over the group index -- every lane of a dim ends with the
-  // same value, in an order fixed by the lane numbers
-#pragma unroll
-  for (int x = LPK; x < 64; x <<= 1) {
-    const float m2 = __shfl_xor(m, x), l2 = __shfl_xor(l, x);
-    const float mn = fmaxf(m, m2);
-    // (both factors from the lower and the upper partner in the same roles on both sides: a + b with a from the lower lane)
-    const bool low = (lane & x) == 0;
-    const float fa = exp2f((low ? m : m2) - mn), fb = exp2f((low ? m2 : m) - mn);
-    l = (low ? l : l2) * fa + (low ? l2 : l) * fb;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float o2 = __shfl_xor(o[e], x);
-      o[e] = (low ? o[e] : o2) * fa + (low ? o2 : o[e]) * fb;
-    }
-    m = mn;
-  }
+  attn_group_merge<LPK>(lane, m, l, o);
   if (grp == 0) {
     if (piece == 0) { sm[wave] = m; sl[wave] = l; }
 #pragma unroll
@@ -373,23 +416,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const
   __syncthreads();
   if (threadIdx.x < D) {
     const int d = threadIdx.x;
-    float mm = sm[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) mm = fmaxf(mm, sm[w]);
-    float ll = 0.f, oo = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float f = exp2f(sm[w] - mm);
-      ll += sl[w] * f;
-      oo += so[w][d] * f;
-    }
-    if (part) {
-      float *pp = part + (((size_t)n * H + h) * S + s) * (D + 2);
-      if (d == 0) { pp[0] = mm; pp[1] = ll; }
-      pp[2 + d] = oo;
-    } else {
-      out[(size_t)n * ldo + (size_t)h * D + d] = f2bf(ll > 0.f ? oo / ll : 0.f);       // no visible key: 0
-    }
+    float mm, ll, oo;
+    attn_wave_merge(sm, sl, &so[0][0], D, d, mm, ll, oo);
+    attn_store<D>(n, h, H, s, S, d, mm, ll, oo, out, ldo, part);
   }
 }
 
@@ -407,6 +436,115 @@ __global__ __launch_bounds__(D) void attn_merge_kernel(int H, int S, const float
     oo += pp[(size_t)s * (D + 2) + 2 + d] * f;
   }
   out[(size_t)n * ldo + (size_t)h * D + d] = f2bf(ll > 0.f ? oo / ll : 0.f);
+}
+
+// ---- decode attention, the prompt's keys stored once per prompt ---------------------------------------------------
+// The G rows of prompt b (beams) share its T prompt slots (kp, vp (B, T, H, D), pkeep (B, T)) and differ only in their
+// tails (kt, vt (B G, Ttail, H, D)); all G have the same length L = T + tail, so the split bounds and the key -> (wave,
+// lane group) assignment of attn_decode_kernel are the same for all of them.  grid (H, B ceil(G / 8), S): a workgroup
+// serves R <= 8 rows of one prompt (R = G up to 8 rows; above that chunks of 8, the last one partly idle), with every
+// row's online-softmax state in registers.  It walks the keys exactly as attn_decode_kernel does for ONE row -- the same
+// waves, steps and lane groups -- and applies each key to its R queries with the helpers above: per row the same
+// operations on the same values in the same order, so the bits of attn_decode_kernel on the materialised cache.  A wave
+// step (KPW keys) that lies wholly inside the prompt issues one K and one V load for all R rows; one that straddles T or
+// lies in the tail loads per row.
+template <int D, int R>
+__global__ __launch_bounds__(256) void attn_decode_shared_kernel(int G, int T, int Ttail, int H, const u16 *__restrict__ q,
+                                                                 int ldq, const u16 *__restrict__ kp,
+                                                                 const u16 *__restrict__ vp,
+                                                                 const unsigned char *__restrict__ pkeep,
+                                                                 const u16 *__restrict__ kt, const u16 *__restrict__ vt,
+                                                                 const int *__restrict__ tail_len, int len_add,
+                                                                 float scale_log2, u16 *__restrict__ out, int ldo,
+                                                                 float *__restrict__ part) {
+  constexpr int LPK = D / 8, KPW = 64 / LPK;
+  __shared__ float sm[R][4], sl[R][4], so[R][4][D];
+  const int h = blockIdx.x, s = blockIdx.z, S = gridDim.z;
+  const int chunks = (G + 7) / 8;
+  const int b = blockIdx.y / chunks, g0 = (blockIdx.y % chunks) * 8;
+  const int nr = min(R, G - g0);                      // live rows of this workgroup (< R only in the last chunk of G > 8)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int piece = lane % LPK, grp = lane / LPK;
+  const int L = T + min(max(tail_len[b] + len_add, 0), Ttail);
+  const int t0 = (int)(((long long)L * s) / S), t1 = (int)(((long long)L * (s + 1)) / S);
+  float qf[R][8], m[R], l[R], o[R][8];
+  size_t trow[R];                                     // the row's first tail slot; an idle row reads the chunk's last live one
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const size_t n = (size_t)b * G + g0 + min(r, nr - 1);
+    trow[r] = n * Ttail;
+    unpack8(*reinterpret_cast<const uint4 *>(q + n * ldq + (size_t)h * D + 8 * piece), qf[r]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qf[r][e] *= scale_log2;
+    m[r] = kNegBig, l[r] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[r][e] = 0.f;
+  }
+  const size_t prow = (size_t)b * T;
+  const unsigned char *pk = pkeep ? pkeep + prow : nullptr;
+  constexpr int U = 4;
+  for (int tb = t0 + wave * KPW; tb < t1; tb += 4 * KPW * U) {
+    if (tb + (U - 1) * 4 * KPW + KPW <= T) {          // (wave-uniform) all U steps inside the prompt: U loads in flight
+      uint4 kv[U], vv[U];
+      bool on[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int t = tb + u * 4 * KPW + grp;
+        on[u] = t < t1 && (!pk || pk[t]);
+        const size_t off = ((prow + (on[u] ? t : t0)) * H + h) * D + 8 * piece;   // (t0 <= tb < T here: in bounds)
+        kv[u] = *reinterpret_cast<const uint4 *>(kp + off);
+        vv[u] = *reinterpret_cast<const uint4 *>(vp + off);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv[u], vv[u], on[u], m[r], l[r], o[r]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ts = tb + u * 4 * KPW, t = ts + grp;
+        if (ts >= t1) break;                          // (wave-uniform)
+        if (ts + KPW <= T) {
+          const bool on = t < t1 && (!pk || pk[t]);
+          const size_t off = ((prow + (on ? t : 0)) * H + h) * D + 8 * piece;     // (T >= 1: slot 0 exists)
+          const uint4 kv = *reinterpret_cast<const uint4 *>(kp + off), vv = *reinterpret_cast<const uint4 *>(vp + off);
+#pragma unroll
+          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv, vv, on, m[r], l[r], o[r]);
+        } else {
+          // a lane's key is a prompt slot (t < T) or the row's own tail slot t - T < Ttail (t < t1 <= L); a lane
+          // without a key reads prompt slot 0
+          const bool tail = t >= T;
+          const bool on = t < t1 && (tail || !pk || pk[t]);
+          uint4 kv[R], vv[R];
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            const bool tl = on && tail;
+            const size_t off = (((tl ? trow[r] + (size_t)(t - T) : prow + (on ? t : 0))) * H + h) * D + 8 * piece;
+            kv[r] = *reinterpret_cast<const uint4 *>((tl ? kt : kp) + off);
+            vv[r] = *reinterpret_cast<const uint4 *>((tl ? vt : vp) + off);
+          }
+#pragma unroll
+          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv[r], vv[r], on, m[r], l[r], o[r]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    attn_group_merge<LPK>(lane, m[r], l[r], o[r]);
+    if (grp == 0) {
+      if (piece == 0) { sm[r][wave] = m[r]; sl[r][wave] = l[r]; }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) so[r][wave][8 * piece + e] = o[r][e];
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nr * D; i += 256) {
+    const int r = i / D, d = i % D;
+    float mm, ll, oo;
+    attn_wave_merge(sm[r], sl[r], &so[r][0][0], D, d, mm, ll, oo);
+    attn_store<D>(b * G + g0 + r, h, H, s, S, d, mm, ll, oo, out, ldo, part);
+  }
 }
 
 // ---- cache gather -----------------------------------------------------------------------------------------------
@@ -519,6 +657,26 @@ __global__ __launch_bounds__(256) void decode_select_kernel(int V, const u16 *__
     }
     __syncthreads();
   }
+}
+
+// the instantiation for `rows_per_wg` = min(G, 8) rows a workgroup
+template <int D>
+void attn_decode_shared_launch(int rows_per_wg, dim3 grid, hipStream_t st, int G, int T, int Ttail, int H, const u16 *q,
+                                      int ldq, const u16 *kp, const u16 *vp, const unsigned char *pkeep, const u16 *kt,
+                                      const u16 *vt, const int *tail_len, int len_add, float sl2, u16 *out, int ldo,
+                                      float *part) {
+#define MSR3D_ADS(R)                                                                                                   \
+  case R:                                                                                                              \
+    attn_decode_shared_kernel<D, R><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, kp, vp, pkeep, kt, vt, tail_len,     \
+                                                          len_add, sl2, out, ldo, part);                               \
+    break;
+  switch (rows_per_wg) {
+    MSR3D_ADS(1) MSR3D_ADS(2) MSR3D_ADS(3) MSR3D_ADS(4) MSR3D_ADS(5) MSR3D_ADS(6) MSR3D_ADS(7)
+    default:
+      attn_decode_shared_kernel<D, 8><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, kp, vp, pkeep, kt, vt, tail_len, len_add,
+                                                            sl2, out, ldo, part);
+  }
+#undef MSR3D_ADS
 }
 
 }  // namespace
@@ -654,6 +812,42 @@ int msr3d_attn_decode(int N, int Tmax, int H, int D, const void *q, int ldq, con
   if (S > 1) {
     if (D == 128) attn_merge_kernel<128><<<dim3(H, N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
     else attn_merge_kernel<64><<<dim3(H, N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
+  }
+  return (int)hipGetLastError();
+}
+
+int msr3d_attn_decode_shared(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq, const void *k_prompt,
+                             const void *v_prompt, const unsigned char *prompt_keep, const void *k_tail, const void *v_tail,
+                             const int *tail_len, int len_add, float scale, void *out, int ldo, float *workspace,
+                             long long workspace_floats, int splits, msr3d_stream_t stream) {
+  if (B < 0 || G <= 0 || T <= 0 || Ttail < 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) || ldo < H * D ||
+      splits < 0 || splits > MSR3D_ATTN_DECODE_MAX_SPLITS)
+    return MSR3D_EINVAL;
+  if (B == 0) return 0;
+  const long long N = (long long)B * G, gy = (long long)B * ((G + 7) / 8);
+  if (N > 65535 || gy > 65535 || !q || !k_prompt || !v_prompt || !tail_len || !out || !al16(q) || !al16(k_prompt) ||
+      !al16(v_prompt))
+    return MSR3D_EINVAL;
+  if (Ttail > 0 && (!k_tail || !v_tail || !al16(k_tail) || !al16(v_tail))) return MSR3D_EINVAL;
+  // splits 0: what msr3d_attn_decode takes for these N rows (one split without a workspace)
+  const int S = splits ? splits : (workspace ? msr3d_attn_decode_splits((int)N, H) : 1);
+  if (S > 1 && (!workspace || workspace_floats < N * H * S * (D + 2))) return MSR3D_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(H, (unsigned)gy, S);
+  float *part = S > 1 ? workspace : nullptr;
+  const int rows_per_wg = G < 8 ? G : 8;
+  if (D == 128)
+    attn_decode_shared_launch<128>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, (const u16 *)k_prompt,
+                                   (const u16 *)v_prompt, prompt_keep, (const u16 *)k_tail, (const u16 *)v_tail, tail_len,
+                                   len_add, sl2, (u16 *)out, ldo, part);
+  else
+    attn_decode_shared_launch<64>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, (const u16 *)k_prompt,
+                                  (const u16 *)v_prompt, prompt_keep, (const u16 *)k_tail, (const u16 *)v_tail, tail_len,
+                                  len_add, sl2, (u16 *)out, ldo, part);
+  if (S > 1) {
+    if (D == 128) attn_merge_kernel<128><<<dim3(H, (unsigned)N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
+    else attn_merge_kernel<64><<<dim3(H, (unsigned)N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
   }
   return (int)hipGetLastError();
 }

@@ -15,7 +15,9 @@ Four pieces:
 * `KVCache`        the buffers of one call: K / V (layers, 2, rows, t_max, heads, head_dim) bf16, token-major like the
                    projections' own output, twice when beams are reordered (ping-pong), and per row `len` (cache slots in
                    use), `pos` (the next rotary position = number of unmasked tokens so far) and `keep` (key padding).
-                   Allocated once per call, never resized.
+                   Allocated once per call, never resized.  layout "shared" (`prompt_cache="shared"`): the prompt's K / V
+                   once per PROMPT (layers, 2, prompts, T, heads, head_dim), never reordered, and only the generated
+                   tails per row -- the beams of a prompt read one copy (msr3d_attn_decode_shared), the same bits.
 * `CachedDecoder`  the engine: `prefill` runs the existing layer forward kernels over the padded prompt (positions =
                    cumsum(mask) - 1, clamped at 0: what transformers' generate feeds Llama when it is given a mask) and
                    writes every layer's K / V into the cache; `step` runs one token per live row: per layer RMSNorm,
@@ -467,25 +469,63 @@ def rank_answers(engine, embed_fn, inputs_embeds, attention_mask, answer_ids, an
 
 # ------------------------------------------------------------------------------------------------------------ cache
 class KVCache:
-    """kv[side] (layers, 2, rows, t_max, heads, head_dim) bf16, side = `cur` is the live one (two sides only with
-    `pingpong`: msr3d_kv_reorder gathers from one into the other); len, pos (rows) int32; keep (rows, t_max) uint8."""
+    """layout "rows": kv[side] (layers, 2, rows, t_max, heads, head_dim) bf16, side = `cur` is the live one (two sides only
+    with `pingpong`: msr3d_kv_reorder gathers from one into the other); len, pos (rows) int32; keep (rows, t_max) uint8.
 
-    def __init__(self, layers, rows, t_max, heads, head_dim, device, pingpong=False):
+    layout "shared" (`prompts` prompts of rows / prompts adjacent rows each, `t_prompt` prompt slots): a prompt's keys
+    are written once by the prefill and are the same in all of its rows for ever, so they are stored once --
+    prompt_kv (layers, 2, prompts, t_prompt, heads, head_dim), one side, never reordered, with prompt_keep (prompts,
+    t_prompt) -- and only the generated tail is per row: kv[side] (layers, 2, rows, t_max - t_prompt, heads, head_dim),
+    ping-ponged like the rows layout's.  `len` (rows) counts TAIL slots (what msr3d_rope_kv_append and msr3d_kv_reorder
+    read on the tail planes) and `tail_len` (prompts) is the same number per prompt (what msr3d_attn_decode_shared
+    reads): all rows of a prompt have the same length at every step, and a reorder permutes rows within a prompt, so
+    neither is reordered.  `pos` is as in the rows layout."""
+
+    def __init__(self, layers, rows, t_max, heads, head_dim, device, pingpong=False, layout="rows", prompts=None,
+                 t_prompt=None):
+        if layout not in ("rows", "shared"):
+            raise ValueError(f"KVCache: layout is 'rows' or 'shared', not {layout!r}")
         self.layers, self.rows, self.t_max, self.heads, self.head_dim = layers, rows, t_max, heads, head_dim
+        self.layout = layout
         sides = 2 if pingpong else 1
-        self.kv = [torch.zeros((layers, 2, rows, t_max, heads, head_dim), dtype=torch.bfloat16, device=device)
-                   for _ in range(sides)]
-        self.cur = 0
+        bf = torch.bfloat16
         mk = lambda *s, dt: [torch.zeros(s, dtype=dt, device=device) for _ in range(sides)]     # noqa: E731
-        self._len, self._pos = mk(rows, dt=torch.int32), mk(rows, dt=torch.int32)
-        self._keep = [torch.ones((rows, t_max), dtype=torch.uint8, device=device) for _ in range(sides)]
+        self._pos = mk(rows, dt=torch.int32)
+        if layout == "rows":
+            self.kv = [torch.zeros((layers, 2, rows, t_max, heads, head_dim), dtype=bf, device=device) for _ in range(sides)]
+            self._len = mk(rows, dt=torch.int32)
+            self._keep = [torch.ones((rows, t_max), dtype=torch.uint8, device=device) for _ in range(sides)]
+        else:
+            if not prompts or rows % prompts or not t_prompt or not 0 < t_prompt < t_max:
+                raise ValueError("KVCache: layout='shared' takes prompts (a divisor of rows) and 0 < t_prompt < t_max")
+            self.prompts, self.t_prompt, self.t_tail = int(prompts), int(t_prompt), int(t_max - t_prompt)
+            self.prompt_kv = torch.zeros((layers, 2, prompts, t_prompt, heads, head_dim), dtype=bf, device=device)
+            self.prompt_keep = torch.ones((prompts, t_prompt), dtype=torch.uint8, device=device)
+            self.kv = [torch.zeros((layers, 2, rows, self.t_tail, heads, head_dim), dtype=bf, device=device)
+                       for _ in range(sides)]
+            # one buffer, so that one add_ advances both views: [rows tail lengths | prompts tail lengths]
+            self._lens = torch.zeros(rows + prompts, dtype=torch.int32, device=device)
+        self.cur = 0
         splits = _lib.load().msr3d_attn_decode_splits(rows, heads)
         self.workspace = (torch.empty(rows * heads * splits * (head_dim + 2), dtype=torch.float32, device=device)
                           if splits > 1 else None)
 
-    len = property(lambda self: self._len[self.cur])
+    len = property(lambda self: self._len[self.cur] if self.layout == "rows" else self._lens[:self.rows])
     pos = property(lambda self: self._pos[self.cur])
     keep = property(lambda self: self._keep[self.cur])
+    tail_len = property(lambda self: self._lens[self.rows:])
+
+    @property
+    def nbytes(self):
+        """The bytes of the K / V planes allocated (every side, and the prompt planes of the shared layout); the lengths,
+        positions, key padding and the split workspace beside them are KB."""
+        n = sum(t.numel() * t.element_size() for t in self.kv)
+        return n + (self.prompt_kv.numel() * self.prompt_kv.element_size() if self.layout == "shared" else 0)
+
+    def advance(self):
+        """One more slot in use and one more position, in every row."""
+        (self._len[self.cur] if self.layout == "rows" else self._lens).add_(1)
+        self.pos.add_(1)
 
     def k(self, layer):
         return self.kv[self.cur][layer, 0]
@@ -494,17 +534,18 @@ class KVCache:
         return self.kv[self.cur][layer, 1]
 
     def reorder(self, beam_idx):
-        """Row n continues row beam_idx[n]: one launch for every layer's K and V, into the other side."""
+        """Row n continues row beam_idx[n]: one launch for every layer's K and V, into the other side.  Shared layout:
+        the tail planes alone, and beam_idx[n] must be a row of n's own prompt (what beam search produces)."""
         if len(self.kv) < 2:
             raise RuntimeError("KVCache: allocated without the second side (pingpong=True) a reorder needs")
         idx = beam_idx.to(torch.int32).contiguous()
         src, dst = self.kv[self.cur], self.kv[1 - self.cur]
         dev = src.device
         with torch.cuda.device(dev):
-            call("msr3d_kv_reorder", self.layers * 2, self.rows, self.t_max, self.heads * self.head_dim, ptr(src), ptr(dst),
+            call("msr3d_kv_reorder", self.layers * 2, self.rows, src.shape[3], self.heads * self.head_dim, ptr(src), ptr(dst),
                  ptr(idx), ptr(self.len), current_stream_ptr(dev))
         il = idx.long()
-        for pair in (self._len, self._pos, self._keep):
+        for pair in ((self._len, self._pos, self._keep) if self.layout == "rows" else (self._pos,)):
             torch.index_select(pair[self.cur], 0, il, out=pair[1 - self.cur])
         self.cur = 1 - self.cur
 
@@ -605,14 +646,22 @@ class CachedDecoder:
     graph's arithmetic; "merged": every product on the stack's merged planes (MergedModuleProducts /
     MergedSkinnyProducts; LoRALlamaStack.merged_weights states cost and staleness).  The strategy is chosen at every
     prefill / score -- where the planes are rebuilt if a weight has been written since -- and kept for the steps that
-    follow."""
+    follow.
+    prompt_cache = "rows": every live row carries its own copy of the prompt's keys and values; "shared": with more
+    than one row per prompt (beams, captions) the prompt is stored once per prompt and only the generated tail per row
+    (KVCache layout "shared"): `expand` copies no K / V, a beam reorder gathers the tails alone, and the step attends
+    with msr3d_attn_decode_shared, which loads a prompt key once for up to 8 rows.  Every logit of every step is
+    bit-identical to "rows".  With one row per prompt there is nothing to share and the rows layout is used (`score`
+    always sees it)."""
 
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
-    def __init__(self, stack, lora="separate"):
+    def __init__(self, stack, lora="separate", prompt_cache="rows"):
         if lora not in ("separate", "merged"):
             raise ValueError(f"lora is 'separate' or 'merged', not {lora!r}")
-        self.stack, self.lora = stack, lora
+        if prompt_cache not in ("rows", "shared"):
+            raise ValueError(f"prompt_cache is 'rows' or 'shared', not {prompt_cache!r}")
+        self.stack, self.lora, self.prompt_cache = stack, lora, prompt_cache
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
         if any(m.base == "fp8" for m in self.mods):
             raise NotImplementedError("CachedDecoder: base='fp8' stacks are not supported (the decode products read the bf16 "
@@ -666,7 +715,12 @@ class CachedDecoder:
         else:
             raise ValueError("CachedDecoder.prefill: positions is 'mask' or 'arange'")
         t_max = T + new_tokens
-        cache = self.cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1)
+        shared = self.prompt_cache == "shared" and beams > 1 and new_tokens > 0       # (one row a prompt: nothing to share)
+        if shared:
+            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=True, layout="shared", prompts=B, t_prompt=T)
+        else:
+            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1)
+        self.cache = cache
         rows = max(t_max, Tp)
         cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
         self._tables = (cos, sin, rows)
@@ -680,14 +734,21 @@ class CachedDecoder:
                 call("msr3d_rope_positions", B, Tp, H, D, ptr(q), ptr(k), ptr(pos), ptr(cos), ptr(sin), rows,
                      current_stream_ptr(dev))
             q, k, v = q.view(B, Tp, H, D), k.view(B, Tp, H, D), v.view(B, Tp, H, D)
-            cache.k(i)[first, :T] = k[:, :T]
-            cache.v(i)[first, :T] = v[:, :T]
+            if shared:                        # straight into the prompt planes: the one copy every row of the prompt reads
+                cache.prompt_kv[i, 0] = k[:, :T]
+                cache.prompt_kv[i, 1] = v[:, :T]
+            else:
+                cache.k(i)[first, :T] = k[:, :T]
+                cache.v(i)[first, :T] = v[:, :T]
             return _AttentionFn.apply(q, k, v, keep)
 
         logits = decoder_stack(st, x, attend, products, slice(T - 1, T))           # only the last position's are wanted
-        cache.len[first] = T
         cache.pos[first] = mask.sum(-1).to(torch.int32) if positions == "mask" else T
-        cache.keep[first, :T] = keep[:, :T]
+        if shared:                            # (the tails are empty: len and tail_len stay 0)
+            cache.prompt_keep.copy_(keep[:, :T])
+        else:
+            cache.len[first] = T
+            cache.keep[first, :T] = keep[:, :T]
         return logits[:, 0]
 
     def expand(self, beams):
@@ -697,9 +758,13 @@ class CachedDecoder:
         if beams == 1:
             return
         B, T = c.rows // beams, int(c.t_max - self._plan[1])
-        kv = c.kv[c.cur].view(c.layers, 2, B, beams, c.t_max, c.heads, c.head_dim)
-        kv[:, :, :, 1:, :T] = kv[:, :, :, :1, :T]
-        for t in (c.len, c.pos, c.keep):
+        if c.layout == "shared":              # no K / V to copy: the prompt planes serve every row
+            rows = (c.pos,)
+        else:
+            kv = c.kv[c.cur].view(c.layers, 2, B, beams, c.t_max, c.heads, c.head_dim)
+            kv[:, :, :, 1:, :T] = kv[:, :, :, :1, :T]
+            rows = (c.len, c.pos, c.keep)
+        for t in rows:
             g = t.view(B, beams, *t.shape[1:])
             g[:, 1:] = g[:, :1]
 
@@ -785,6 +850,14 @@ class CachedDecoder:
             ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=dev)
             with torch.cuda.device(dev):
                 s = current_stream_ptr(dev)
+                if c.layout == "shared":      # the append on the tail planes; splits 0 = what the rows layout takes
+                    call("msr3d_rope_kv_append", N, H, D, c.t_tail, ptr(q), ptr(k), ptr(v), HD, ptr(c.pos), ptr(c.len),
+                         ptr(cos), ptr(sin), rows, ptr(c.k(i)), ptr(c.v(i)), s)
+                    call("msr3d_attn_decode_shared", c.prompts, N // c.prompts, c.t_prompt, c.t_tail, H, D, ptr(q), HD,
+                         ptr(c.prompt_kv[i, 0]), ptr(c.prompt_kv[i, 1]), ptr(c.prompt_keep), ptr(c.k(i)), ptr(c.v(i)),
+                         ptr(c.tail_len), 1, ctypes.c_float(scale), ptr(ctx), HD, ptr(ws),
+                         ws.numel() if ws is not None else 0, 0, s)
+                    return ctx
                 call("msr3d_rope_kv_append", N, H, D, c.t_max, ptr(q), ptr(k), ptr(v), HD, ptr(c.pos), ptr(c.len), ptr(cos),
                      ptr(sin), rows, ptr(c.k(i)), ptr(c.v(i)), s)
                 call("msr3d_attn_decode", N, c.t_max, H, D, ptr(q), HD, ptr(c.k(i)), ptr(c.v(i)), ptr(c.len), 1, ptr(c.keep),
@@ -792,8 +865,7 @@ class CachedDecoder:
             return ctx
 
         logits = decoder_stack(st, x, attend, products)
-        c.len.add_(1)
-        c.pos.add_(1)
+        c.advance()
         return logits
 
     def select(self, logits, prev, repetition_penalty, min_length, eos_id, beam_score, order, k):
@@ -859,11 +931,13 @@ class CachedDecoder:
 
 
 @torch.no_grad()
-def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", **search_kwargs):
+def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", **search_kwargs):
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); lora: the
-    engine's products, "separate" or "merged" (CachedDecoder); search_kwargs: everything `search` takes (do_sample, top_p,
-    top_k, temperature, num_return_sequences, seed, draw among them)."""
-    return search(CachedDecoder(stack, lora=lora), _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
+    engine's products, "separate" or "merged", and prompt_cache: its cache layout, "rows" or "shared" -- the same tokens
+    either way (CachedDecoder); search_kwargs: everything `search` takes (do_sample, top_p, top_k, temperature,
+    num_return_sequences, seed, draw among them)."""
+    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache), _embed_fn(embed_tokens), inputs_embeds,
+                  attention_mask, **search_kwargs)
 
 
 @torch.no_grad()

@@ -169,7 +169,7 @@ class LoRALlamaStack(nn.Module):
             for m in mods:
                 m._fresh_in_capture = False
 
-    def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", **search_kwargs):
+    def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", **search_kwargs):
         """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
         -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
         (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
@@ -180,9 +180,13 @@ class LoRALlamaStack(nn.Module):
         whole prompts one after another (the same tokens).
         lora = "separate" (default): the low-rank term is computed beside the frozen weight, as in training;
         lora = "merged": every product streams the merged plane bf16(W + s B A) of `merged_weights()` alone (no r-row
-        launches; one more copy of the projections in memory; the weights rounded once more, so other bits)."""
+        launches; one more copy of the projections in memory; the weights rounded once more, so other bits).
+        prompt_cache = "rows" (default): every live row has its own copy of the prompt's keys and values;
+        prompt_cache = "shared": one copy per prompt and the generated tail per row (a beam reorder moves the tails
+        alone, the attention loads a prompt key once for a prompt's rows) -- the same bits, so the same tokens."""
         from .generate import generate
-        return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, **search_kwargs)
+        return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, prompt_cache=prompt_cache,
+                        **search_kwargs)
 
     def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
                         **rank_kwargs):

@@ -9,6 +9,9 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
     python tools/bench_generate.py --sample      # the draw kernel beside the select kernel and a decode step
     python tools/bench_generate.py --lora both   # + the step on merged weights (lora="merged"), alternating with the
                                                  #   separate one; the merge launch; launches per step; the fresh-call cost
+    python tools/bench_generate.py --prompt-cache both   # a BEAM step (5 rows a prompt, a reorder in it) under the rows
+                                                 #   layout and under prompt_cache="shared", alternating; bytes of either
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --prompt-cache shared --profile 20x576
 """
 import argparse
 import json
@@ -129,6 +132,80 @@ def step_bytes(layers, rows, length):
     return layers * (per_layer + cache) + 2 * HIDDEN * VOCAB
 
 
+BEAMS = 5
+
+
+def beam_bytes(layers, prompts, length, tail):
+    """What the attention reads and the reorder reads + writes in one beam step at `tail` generated tokens, per layout."""
+    tok = layers * 2 * HIDDEN * 2                                   # one token-row: K and V of every layer, bf16
+    rows = prompts * BEAMS
+    return {"rows": {"attention": rows * (length + tail) * tok, "reorder": 2 * rows * (length + tail) * tok},
+            "shared": {"attention": (prompts * length + rows * tail) * tok, "reorder": 2 * rows * tail * tok}}
+
+
+def prompt_cache_cells(args):
+    """--prompt-cache: one decode step WITH a beam reorder in it (beam_idx rotates the rows within every prompt), 5 rows a
+    prompt, under the rows layout (every row its own copy of the prompt) and under prompt_cache="shared", alternating
+    repeat by repeat in one process.  A row count that is no multiple of 5 runs as the whole prompts that fit (64 -> 60).
+    The cache grows by one token per repeat in both; the bytes are stated at the middle repeat."""
+    net = build(args.layers)
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    layouts = ["rows", "shared"] if args.prompt_cache == "both" else [args.prompt_cache]
+    rows_arg = args.rows if args.rows != "1,5,20,32,40,64" else "5,20,40,64"
+    grid = [(int(r), int(t)) for r in rows_arg.split(",") for t in args.lengths.split(",")]
+    if args.profile:
+        grid = [tuple(int(v) for v in args.profile.split("x"))]
+    warmup = 3
+    out = {"bench": "generate_prompt_cache", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
+           "heads": HEADS, "beams": BEAMS, "repeats": args.repeats, "copy_rate_TBps": COPY_RATE / 1e12, "layouts": layouts,
+           "cells": []}
+    for want, length in grid:
+        prompts = max(1, want // BEAMS)
+        rows = prompts * BEAMS
+        x = (torch.randn(prompts, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(prompts, length, dtype=torch.int64, device="cuda")
+        tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+        g = torch.arange(rows, device="cuda")
+        beam_idx = (g // BEAMS) * BEAMS + (g % BEAMS + 1) % BEAMS       # every row continues its neighbour in the prompt
+        engines = []
+        for layout in layouts:
+            eng = CachedDecoder(net, prompt_cache=layout)
+            eng.reserve(BEAMS, args.repeats + warmup + 8)
+            eng.prefill(x, mask)
+            eng.expand(BEAMS)
+            engines.append(eng)
+        fns = [lambda e=e: e.step(tok, beam_idx) for e in engines]
+        if args.profile:
+            for _ in range(20):
+                for fn in fns:
+                    fn()
+            torch.cuda.synchronize()
+            stats = [None] * len(fns)
+        else:
+            stats = timed_alternating(fns, args.repeats, warmup=warmup)
+        tail = warmup + args.repeats // 2
+        cell = {"live_rows": rows, "prompts": prompts, "length": length, "tail_at_middle": tail,
+                "splits": _lib.load().msr3d_attn_decode_splits(rows, HEADS),
+                "attention_workgroups": {"rows": rows * HEADS, "shared": prompts * HEADS}}
+        nbytes = beam_bytes(args.layers, prompts, length, tail)
+        weights = step_bytes(args.layers, 0, 0)
+        for layout, eng, st in zip(layouts, engines, stats):
+            b = nbytes[layout]
+            floor = (weights + b["attention"] + b["reorder"]) / COPY_RATE * 1e6
+            cell[layout] = {"step": st, "attention_bytes": b["attention"], "reorder_bytes": b["reorder"],
+                            "cache_bytes": eng.cache.nbytes, "floor_us": round(floor, 1)}
+            if st is not None:
+                cell[layout]["floor_fraction"] = round(floor / st["median_us"], 3)
+        if len(layouts) == 2 and stats[0] is not None:
+            cell["shared_over_rows"] = round(stats[1]["median_us"] / stats[0]["median_us"], 3)
+            if "launches" not in out:
+                out["launches"] = {n: library_launches(fn) for n, fn in zip(layouts, fns)}
+        out["cells"].append(cell)
+        del engines, fns
+    print(json.dumps(out))
+
+
 def sample_cells(args):
     """--sample: one msr3d_decode_sample launch beside one msr3d_decode_select launch on the same logits (8 previous
     tokens, repetition penalty 3), and a decode step followed by either, at the two shapes decoding has: 64 rows drawing
@@ -172,10 +249,14 @@ def main():
     ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
     ap.add_argument("--lora", default="separate", choices=("separate", "merged", "both"),
                     help="the engine's products; both: the two steps timed in turn in one process")
+    ap.add_argument("--prompt-cache", default="", choices=("", "rows", "shared", "both"),
+                    help="time a beam step (5 rows a prompt, a reorder in it) under that cache layout; both: in turn")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
     if args.sample:
         return sample_cells(args)
+    if args.prompt_cache:
+        return prompt_cache_cells(args)
     net = build(args.layers)
     emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
     gen = torch.Generator(device="cuda").manual_seed(1)
