@@ -1149,6 +1149,19 @@ int msr3d_lora_merge(int njobs, const msr3d_lora_merge_job_t *jobs_device, msr3d
  *   or four 16-row activation tiles per workgroup, with 32 rows of W per workgroup wherever that leaves >= 256
  *   workgroups.  A row of C is computed from that row of P and P2 alone; rows >= M are read clamped and never stored.
  *   msr3d_bf16_skinny_lowrank itself still refuses M > MSR3D_SKINNY_MAX_M.
+ * msr3d_fp8_skinny_lowrank (csrc/llm_decode_fp8.hip; added within ABI v39, nothing else changed): the same product on
+ *   OCP e4m3 weights, half the stream: C_j (M, N_j) bf16 = diag(sp) (Pq Wq_j^T) diag(sw_j) + P2 B2_j^T for njobs <= 3
+ *   weights.  Pq (M, K) e4m3 codes and sp (M) f32 row scales: exactly what msr3d_bf16_gemm_skinny_quant writes; Wq_j
+ *   (N_j, K) e4m3 codes, k-contiguous, and sw_j (N_j) f32 per-output-channel scales: what msr3d_quant_rows_fp8 writes
+ *   for a weight; P2 (M, R), B2_j (N_j, R) bf16 as above (R = 0 or B2_j NULL: no low-rank term).
+ *   0 <= M <= MSR3D_SKINNY_WIDE_MAX_M behind this ONE entry, K % 128 == 0, R % 32 == 0, N_j % 16 == 0, ldp and ldw_j
+ *   >= K and % 16 == 0 (bytes), ldp2 and ldb2_j >= R and % 8 == 0, ldc_j >= N_j; Pq, Wq_j, P2, B2_j 16-byte aligned.
+ *   v_mfma_scale_f32_16x16x128_f8f6f4 (block scales 2^0) with the activations as the 16-row side, a lane's 32 bytes of
+ *   a weight row loaded non-temporally straight into the operand; the four waves split K in 128-wide steps, partial
+ *   sums meet through LDS in wave order; the low-rank pair on the bf16 instruction in accumulators of its own:
+ *   C = bf16(fma(e4m3 sum, sp[m] sw[n], low-rank sum)).  swiglu: as above, the same epilogue and roundings.  A row of
+ *   C comes from that row of Pq, sp and P2 alone and its bits depend on neither M nor the other jobs of the launch;
+ *   rows >= M are read clamped and never stored.  No atomics.  M == 0 or njobs == 0: 0 without a launch.
  * msr3d_rope_positions: x0 and (optional) x1 (B, T, H, D) bf16 rotated in place by pos (B, T) int32 (clamped to
  *   0 .. table_rows - 1); cos / sin (table_rows, D) f32 as msr3d_rope_inplace reads; D % 16 == 0.  pos == arange(T): the
  *   bits of msr3d_rope_inplace2.
@@ -1216,6 +1229,15 @@ int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const
                               const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
 int msr3d_bf16_skinny_lowrank_wide(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
                                    const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
+typedef struct {
+  const void *Wq; int ldw;     /* (N, K) e4m3 codes */
+  const float *sw;             /* (N) f32: one scale per output channel */
+  const void *B2; int ldb2;    /* (N, R) bf16 or NULL */
+  void *C; int ldc;            /* (M, N) bf16 */
+  int N;
+} msr3d_fp8_skinny_job_t;
+int msr3d_fp8_skinny_lowrank(int M, int K, int R, const void *Pq, int ldp, const float *sp, const void *P2, int ldp2,
+                             int njobs, const msr3d_fp8_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
 int msr3d_rope_positions(int B, int T, int H, int D, void *x0, void *x1, const int *pos, const float *cos_td,
                          const float *sin_td, int table_rows, msr3d_stream_t stream);
 int msr3d_rope_kv_append(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,

@@ -58,6 +58,12 @@ class SkinnyJob(ctypes.Structure):
     _fields_ = [("W", _ptr), ("ldw", _c_int), ("B2", _ptr), ("ldb2", _c_int), ("C", _ptr), ("ldc", _c_int), ("N", _c_int)]
 
 
+class Fp8SkinnyJob(ctypes.Structure):
+    """msr3d_fp8_skinny_job_t (include/msr3d_hip.h)."""
+    _fields_ = [("Wq", _ptr), ("ldw", _c_int), ("sw", _ptr), ("B2", _ptr), ("ldb2", _c_int), ("C", _ptr), ("ldc", _c_int),
+                ("N", _c_int)]
+
+
 class LoraShadowJob(ctypes.Structure):
     """msr3d_lora_shadow_job_t (include/msr3d_hip.h)."""
     _fields_ = [("A", _ptr), ("B", _ptr), ("a_pad", _ptr), ("b2", _ptr), ("bt_pad", _ptr), ("at2", _ptr),
@@ -164,6 +170,8 @@ _SIGNATURES = {
                                   _c_int, _ptr],
     "msr3d_bf16_skinny_lowrank_wide": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int,
                                        ctypes.POINTER(SkinnyJob), _c_int, _ptr],
+    "msr3d_fp8_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int,
+                                 ctypes.POINTER(Fp8SkinnyJob), _c_int, _ptr],
     "msr3d_rope_positions": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
     "msr3d_rope_kv_append": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr,
                              _ptr, _ptr],

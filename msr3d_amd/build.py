@@ -49,6 +49,7 @@ SOURCES = [
     ("llm_layer.hip", []),
     ("llm_attn.hip", []),
     ("llm_decode.hip", []),
+    ("llm_decode_fp8.hip", []),
     ("llm_sample.hip", []),
     ("prompter_rows.hip", ["-ffp-contract=off"]),
     ("anchor_front.hip", ["-ffp-contract=off"]),

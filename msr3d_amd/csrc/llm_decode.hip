@@ -4,6 +4,8 @@
 //
 //     msr3d_bf16_skinny_lowrank   C (M <= 32, N) = P W^T + P2 B2^T      every projection and the head: a weight stream
 //     msr3d_bf16_skinny_lowrank_wide   the same for M <= 64: three and four activation tiles a workgroup
+//     msr3d_fp8_skinny_lowrank    the same product on e4m3 weights and row-quantised activations, M <= 64, half the
+//                                 stream (llm_decode_fp8.hip: this file's skinny_kernel on the MX fp8 instruction)
 //     msr3d_rope_kv_append        rotate q, k by the row's own position, write k, v into cache slot len[n]
 //     msr3d_rope_positions        the prefill twin: (B, T, H, D) rotated by pos (B, T)
 //     msr3d_attn_decode           one query row per (row, head) against the row's cache: a stream over K and V

@@ -26,6 +26,8 @@ Four pieces:
                    and positions live in device memory.  Up to `max_rows` = 64 live rows (batch x beams).
                    `lora="merged"`: the same walks on the stack's merged planes bf16(W + s B A) (one msr3d_lora_merge
                    launch per weight version): every product is its R = 0 form and the r-row launches are gone.
+                   `weights="e4m3"`: a base="fp8" stack on its own e4m3 weights (csrc/llm_decode_fp8.hip): the same
+                   launches, the step's projections at half the weight bytes.
 * `search`         greedy / beam search and sampling with transformers' semantics, written against the engine interface alone
                    (`reserve`, `prefill`, `expand`, `step`, and optionally `select` and `sample`), so it runs on the CPU with any
                    engine: that is how its logic is checked exactly against transformers.  A batch with more live rows
@@ -638,10 +640,127 @@ class MergedSkinnyProducts:
     head = staticmethod(SkinnyProducts.head)
 
 
+# ------------------------------------------------------------------------------------------- the same on e4m3 weights
+E4M3_SLAB = 64          # MSR3D_SKINNY_WIDE_MAX_M: the rows one msr3d_fp8_skinny_lowrank launch takes
+E4M3_WIDE_MIN = 128     # from here up LoRALinear's own forward multiplies on e4m3 (msr3d_fp8_gemm_lowrank's domain)
+
+
+def _e4m3_skinny_project(h, mods, swiglu, scratch=None):
+    """_skinny_project for base="fp8" modules on their e4m3 images: per input group ONE msr3d_bf16_gemm_skinny_quant launch
+    (the r-row activation u = s h A^T, the e4m3 codes of h and their row scales) and ONE msr3d_fp8_skinny_lowrank launch
+    that streams weight_q / weight_scale of every member -- the launches of the bf16 step, half the weight bytes.
+    h (M <= 64, K) bf16 contiguous.  scratch: a dict that keeps (u, codes, scales) per (M, K) between calls -- nothing
+    reads them after the group's second launch, and the launches of an engine are ordered on one stream, so a step
+    allocates its outputs alone (at a few rows a step is bounded by its host time)."""
+    M, K = h.shape
+    dev = h.device
+    outs, calls = [None] * len(mods), {}
+    for j, m in enumerate(mods):
+        m._sync_weight_t()                                  # (requantises weight_q when the bf16 weight was written)
+        if m.base != "fp8" or m.weight_q is None:
+            raise RuntimeError("weights='e4m3': a projection without an e4m3 image (base='fp8' modules on the GPU only)")
+        calls.setdefault(id(m._group) if m._group is not None else id(m), []).append(j)
+    if swiglu and len(calls) != 1:
+        # gate and up without a shared low-rank activation (see _skinny_project): two products and the SwiGLU launch
+        gate, up = _e4m3_skinny_project(h, mods, False, scratch)
+        act = torch.empty_like(gate)
+        with torch.cuda.device(dev):
+            call("msr3d_swiglu_fwd", gate.numel(), ptr(gate), ptr(up), ptr(act), current_stream_ptr(dev))
+        return [act]
+    for js in calls.values():
+        m0 = mods[js[0]]
+        a_op = m0._group["a_cat"] if m0._group is not None else m0._shadows(forward=True)[0]
+        buf = scratch.get((M, K, dev)) if scratch is not None else None
+        if buf is None:
+            buf = (torch.empty((M, PAD_R), dtype=torch.bfloat16, device=dev),
+                   torch.empty((M, K), dtype=torch.uint8, device=dev), torch.empty((M,), dtype=torch.float32, device=dev))
+            if scratch is not None:
+                scratch[(M, K, dev)] = buf
+        u, hq, sh = buf
+        with torch.cuda.device(dev):
+            call("msr3d_bf16_gemm_skinny_quant", M, a_op.shape[0], K, ptr(h), K, ptr(a_op), K, ptr(u), PAD_R, PAD_R,
+                 ctypes.c_float(m0.scaling), ptr(hq), K, ptr(sh), current_stream_ptr(dev))
+        jobs = (_lib.Fp8SkinnyJob * len(js))()
+        for n, j in enumerate(js):
+            m = mods[j]
+            if not (swiglu and n == 1):
+                outs[j] = torch.empty((M, m.out_features), dtype=torch.bfloat16, device=dev)
+            jobs[n] = _lib.Fp8SkinnyJob(m.weight_q.data_ptr(), K, m.weight_scale.data_ptr(),
+                                        m._shadows(forward=True)[1].data_ptr(), PAD_R,
+                                        outs[j].data_ptr() if outs[j] is not None else 0, m.out_features, m.out_features)
+        with torch.cuda.device(dev):
+            call("msr3d_fp8_skinny_lowrank", M, K, PAD_R, ptr(hq), K, ptr(sh), ptr(u), PAD_R, len(js), jobs, int(swiglu),
+                 current_stream_ptr(dev))
+    return outs
+
+
+class E4m3SkinnyProducts:
+    """SkinnyProducts for a base="fp8" stack (weights="e4m3"): the same input groups and the same launch count, every
+    LoRA projection on msr3d_fp8_skinny_lowrank -- the activations quantised per row in the r-row launch, the weight read
+    as e4m3 codes.  The head is a FrozenLinear without an e4m3 image and stays on the bf16 kernel.  One per engine: it
+    keeps the groups' scratch tensors between steps."""
+
+    def __init__(self):
+        self.scratch = {}
+
+    def project(self, h, mods, swiglu=False):
+        return _e4m3_skinny_project(h, mods, swiglu, self.scratch)
+
+    def gated(self, h, gate, up):
+        return _e4m3_skinny_project(h, (gate, up), True, self.scratch)[0]
+
+    head = staticmethod(SkinnyProducts.head)
+
+
+class E4m3ModuleProducts:
+    """ModuleProducts for an e4m3 engine's prefill and `score`: every LoRA projection multiplies on e4m3, whatever the
+    number of token rows.  From 128 rows up that is the modules' own forward (msr3d_fp8_gemm_lowrank) -- the stack's
+    full forward bit for bit; below, where LoRALinear falls back to its bf16 plane, the rows go through
+    msr3d_fp8_skinny_lowrank in slabs of at most 64.  The two kernels add the same exact e4m3 products in different
+    orders: a walk of fewer than 128 rows may differ from a larger one in last bits.  Evaluation only (no autograd)."""
+
+    @staticmethod
+    def _slabs(h, mods, swiglu):
+        if torch.is_grad_enabled() and h.requires_grad:
+            raise RuntimeError("E4m3ModuleProducts: evaluation only (no backward); call under torch.no_grad()")
+        if not h.is_cuda:
+            raise RuntimeError("LoRALinear runs on the GPU only (no CPU fallback)")
+        x2 = h.to(torch.bfloat16).reshape(-1, h.shape[-1])
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        cols = None                                         # per output, its slabs in row order
+        for s in range(0, x2.shape[0], E4M3_SLAB):
+            part = [o for o in _e4m3_skinny_project(x2[s:s + E4M3_SLAB], mods, swiglu) if o is not None]
+            cols = [[o] for o in part] if cols is None else [c + [o] for c, o in zip(cols, part)]
+        return [c[0] if len(c) == 1 else torch.cat(c, 0) for c in cols]
+
+    @classmethod
+    def project(cls, h, mods):
+        if h.numel() // h.shape[-1] >= E4M3_WIDE_MIN:
+            return ModuleProducts.project(h, mods)
+        return cls._slabs(h, mods, False)
+
+    @classmethod
+    def gated(cls, h, gate, up):
+        if h.numel() // h.shape[-1] >= E4M3_WIDE_MIN:
+            return ModuleProducts.gated(h, gate, up)
+        return cls._slabs(h, (gate, up), True)[0]
+
+    head = staticmethod(ModuleProducts.head)
+
+
 # ----------------------------------------------------------------------------------------------------------- engine
 class CachedDecoder:
-    """The decoding engine of a LoRALlamaStack (see the module docstring).  bf16 base weights only.  At most `max_rows`
-    live rows (batch x beams) per prefill; `search` splits a larger batch into groups of whole prompts.
+    """The decoding engine of a LoRALlamaStack (see the module docstring).  At most `max_rows` live rows (batch x beams)
+    per prefill; `search` splits a larger batch into groups of whole prompts.
+    weights = "bf16" (default): every product reads the bf16 base weights; a base="fp8" stack is refused.
+    weights = "e4m3": a stack whose projections are all base="fp8" decodes on its own e4m3 images -- what its training
+    forward multiplies on: a step streams weight_q / weight_scale through msr3d_fp8_skinny_lowrank (E4m3SkinnyProducts:
+    the same launch count, half the weight bytes; the head stays bf16), prefill and `score` keep every product on e4m3
+    (E4m3ModuleProducts: the modules' own forward from 128 token rows up, slabs of 64 rows on the skinny kernel below).
+    Those two kernels sum in different orders, so under "e4m3" a `score` chunk or a prefill below 128 rows may differ
+    from a larger one in last bits: the results are NOT invariant under chunking and grouping, unlike "bf16".
+    Reproducible call to call (no atomics); prompt_cache "rows" and "shared" still give the same bits.  Not with
+    lora="merged" (no merged e4m3 planes), not for bf16 stacks (no e4m3 images).
     lora = "separate": the low-rank term beside the frozen weight (ModuleProducts / SkinnyProducts), the training
     graph's arithmetic; "merged": every product on the stack's merged planes (MergedModuleProducts /
     MergedSkinnyProducts; LoRALlamaStack.merged_weights states cost and staleness).  The strategy is chosen at every
@@ -656,25 +775,40 @@ class CachedDecoder:
 
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
-    def __init__(self, stack, lora="separate", prompt_cache="rows"):
+    def __init__(self, stack, lora="separate", prompt_cache="rows", weights="bf16"):
         if lora not in ("separate", "merged"):
             raise ValueError(f"lora is 'separate' or 'merged', not {lora!r}")
         if prompt_cache not in ("rows", "shared"):
             raise ValueError(f"prompt_cache is 'rows' or 'shared', not {prompt_cache!r}")
-        self.stack, self.lora, self.prompt_cache = stack, lora, prompt_cache
+        if weights not in ("bf16", "e4m3"):
+            raise ValueError(f"weights is 'bf16' or 'e4m3', not {weights!r}")
+        self.stack, self.lora, self.prompt_cache, self.weights = stack, lora, prompt_cache, weights
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
-        if any(m.base == "fp8" for m in self.mods):
-            raise NotImplementedError("CachedDecoder: base='fp8' stacks are not supported (the decode products read the bf16 "
-                                      "weights; e4m3 decoding is not implemented)")
+        if weights == "bf16":
+            if any(m.base == "fp8" for m in self.mods):
+                raise NotImplementedError("CachedDecoder: base='fp8' stacks are not supported on bf16 products (weights='bf16' "
+                                          "reads the bf16 weights); pass weights='e4m3' to decode on their e4m3 images")
+        else:
+            if lora == "merged":
+                raise NotImplementedError("CachedDecoder: weights='e4m3' with lora='merged' is not supported (base='fp8': a "
+                                          "merged plane requantised to e4m3 would round LoRA deltas below e4m3's 2^-4 "
+                                          "resolution away)")
+            if not self.mods or any(m.base != "fp8" for m in self.mods):
+                raise ValueError("CachedDecoder: weights='e4m3' needs a stack built with base='fp8' (a bf16 stack has no "
+                                 "e4m3 images)")
         if not stack.layers:
             raise ValueError("CachedDecoder: a stack without layers")
         l0 = stack.layers[0]
         self.H, self.D, self.hidden = l0.num_heads, l0.head_dim, l0.hidden_size
         self.cache, self._plan, self._tables = None, (1, 256), None
-        self._wide, self._skinny = ModuleProducts, SkinnyProducts
+        if weights == "e4m3":
+            self._wide, self._skinny = E4m3ModuleProducts, E4m3SkinnyProducts()
+        else:
+            self._wide, self._skinny = ModuleProducts, SkinnyProducts
 
     def _products(self):
-        """The strategies of this call, on current weights: bf16 images of the pairs, or the merged planes."""
+        """The strategies of this call, on current weights: bf16 images of the pairs, or the merged planes (the e4m3
+        images of the frozen weights are requantised by the modules themselves when a weight was written)."""
         if self.lora == "merged":
             planes = self.stack.merged_weights()
             self._wide, self._skinny = MergedModuleProducts(planes), MergedSkinnyProducts(planes)
@@ -776,7 +910,9 @@ class CachedDecoder:
         followed by tokens 0 .. j of candidate c, at rotary positions pos[b] + j.  Every layer runs over the B C S suffix
         rows alone with the layer forward's kernels; attention is msr3d_attn_prefix_fwd against the cached prefix.  The
         cache is read, never written: `score` may be called again after one `prefill`.  Candidates are walked in chunks of
-        at most `max_rows` suffix rows (every row's arithmetic is its own: the result does not depend on the chunking)."""
+        at most `max_rows` suffix rows (every row's arithmetic is its own: the result does not depend on the chunking --
+        except under weights="e4m3", where a chunk of fewer than 128 rows multiplies on another kernel than a larger one
+        and may differ in last bits)."""
         st, c = self.stack, self.cache
         if c is None:
             raise RuntimeError("CachedDecoder.score before prefill")
@@ -931,19 +1067,21 @@ class CachedDecoder:
 
 
 @torch.no_grad()
-def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", **search_kwargs):
+def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
+             **search_kwargs):
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); lora: the
     engine's products, "separate" or "merged", and prompt_cache: its cache layout, "rows" or "shared" -- the same tokens
-    either way (CachedDecoder); search_kwargs: everything `search` takes (do_sample, top_p, top_k, temperature,
-    num_return_sequences, seed, draw among them)."""
-    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache), _embed_fn(embed_tokens), inputs_embeds,
-                  attention_mask, **search_kwargs)
+    either way (CachedDecoder); weights: "bf16", or "e4m3" for a base="fp8" stack on its own e4m3 weights;
+    search_kwargs: everything `search` takes (do_sample, top_p, top_k, temperature, num_return_sequences, seed, draw
+    among them)."""
+    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache, weights=weights), _embed_fn(embed_tokens),
+                  inputs_embeds, attention_mask, **search_kwargs)
 
 
 @torch.no_grad()
 def predict_answers(stack, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
-                    **rank_kwargs):
-    """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder(lora=lora); rank_kwargs: num_ans_candidates,
-    bos_id."""
-    return rank_answers(CachedDecoder(stack, lora=lora), _embed_fn(embed_tokens), inputs_embeds, attention_mask, answer_ids,
-                        answer_mask, **rank_kwargs)
+                    weights="bf16", **rank_kwargs):
+    """LoRALlamaStack.predict_answers: `rank_answers` on a CachedDecoder(lora=lora, weights=weights); rank_kwargs:
+    num_ans_candidates, bos_id."""
+    return rank_answers(CachedDecoder(stack, lora=lora, weights=weights), _embed_fn(embed_tokens), inputs_embeds,
+                        attention_mask, answer_ids, answer_mask, **rank_kwargs)

@@ -169,7 +169,8 @@ class LoRALlamaStack(nn.Module):
             for m in mods:
                 m._fresh_in_capture = False
 
-    def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", **search_kwargs):
+    def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
+                 **search_kwargs):
         """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
         -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
         (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
@@ -183,20 +184,25 @@ class LoRALlamaStack(nn.Module):
         launches; one more copy of the projections in memory; the weights rounded once more, so other bits).
         prompt_cache = "rows" (default): every live row has its own copy of the prompt's keys and values;
         prompt_cache = "shared": one copy per prompt and the generated tail per row (a beam reorder moves the tails
-        alone, the attention loads a prompt key once for a prompt's rows) -- the same bits, so the same tokens."""
+        alone, the attention loads a prompt key once for a prompt's rows) -- the same bits, so the same tokens.
+        weights = "bf16" (default): the products read the bf16 base weights (a base="fp8" stack is refused);
+        weights = "e4m3": a base="fp8" stack decodes on its own e4m3 weights, the ones its training forward multiplies
+        on (CachedDecoder states what that changes: half the step's weight stream; last bits may move with the batch's
+        grouping; not with lora="merged")."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, prompt_cache=prompt_cache,
-                        **search_kwargs)
+                        weights=weights, **search_kwargs)
 
     def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
-                        **rank_kwargs):
+                        weights="bf16", **rank_kwargs):
         """Closed-set answer ranking on one cached copy of every prompt (msr3d_amd/llm/generate.py::rank_answers) ->
         dict(answers_id (B,), topk_ids (B, C), loss (B, C) fp32, first_prob (B, A)).  answer_ids / answer_mask (A, S):
-        the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id; lora: as in
-        `generate`."""
+        the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id; lora and weights: as
+        in `generate` (under weights="e4m3" the losses may move in last bits with num_ans_candidates, which sets the
+        number of suffix rows a `score` chunk multiplies at once)."""
         from .generate import predict_answers
         return predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora=lora,
-                               **rank_kwargs)
+                               weights=weights, **rank_kwargs)
 
     def forward(self, inputs_embeds, attention_mask=None, targets=None, supervised_from=None):
         """-> logits (B, T, V) bf16, or with `targets` (B, T) int64 (negative = not supervised) the per-sequence mean

@@ -139,7 +139,7 @@ class MSR3DFullStep(MSR3DHotPath):
     @torch.no_grad()
     def generate(self, data_dict, num_beams=5, max_length=256, min_length=1, repetition_penalty=3.0, length_penalty=1.0,
                  max_out_len=256, bos_id=1, eos_id=2, use_nucleus_sampling=False, top_p=0.9, temperature=1.0,
-                 num_captions=1, seed=None, top_k=50, lora="separate", prompt_cache="rows"):
+                 num_captions=1, seed=None, top_k=50, lora="separate", prompt_cache="rows", weights="bf16"):
         """The reference's MSR3D.generate: hot path -> prompt embeddings with the scene tokens written in and the object
         mask at their positions (prompt only, no answer) -> one bos embedding and a mask column of ones appended -> beam
         search (or sampling) over the key / value cache (`max_length` counts generated tokens) -> id 0 mapped to 2 ->
@@ -156,7 +156,9 @@ class MSR3DFullStep(MSR3DHotPath):
         lora = "merged": decode on the language model's merged planes bf16(W + s B A) (LoRALlamaStack.merged_weights: one
         more copy of its projections in memory, rebuilt only after a weight was written; no low-rank launches).
         prompt_cache = "shared": the beams (or captions) of a prompt read ONE cached copy of the prompt's keys and values
-        and carry only their generated tails (LoRALlamaStack.generate) -- the same tokens as the default "rows"."""
+        and carry only their generated tails (LoRALlamaStack.generate) -- the same tokens as the default "rows".
+        weights = "e4m3": a model whose language model was built with base="fp8" decodes on its own e4m3 weights (the
+        default "bf16" refuses such a model; LoRALlamaStack.generate)."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if max_length > max_out_len:
@@ -180,7 +182,7 @@ class MSR3DFullStep(MSR3DHotPath):
                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                       do_sample=bool(use_nucleus_sampling), top_p=top_p, top_k=top_k,
                                       temperature=temperature, num_return_sequences=num_captions, seed=seed, lora=lora,
-                                      prompt_cache=prompt_cache)
+                                      prompt_cache=prompt_cache, weights=weights)
         out = torch.where(out == 0, torch.full_like(out, 2), out)
         pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
         d["output_tokens"] = torch.cat([out, pad], 1)
@@ -188,14 +190,14 @@ class MSR3DFullStep(MSR3DHotPath):
 
     @torch.no_grad()
     def predict_answers(self, data_dict, answer_ids, answer_mask, num_ans_candidates=128, bos_id=1, answer_list=None,
-                        lora="separate"):
+                        lora="separate", weights="bf16"):
         """The reference's MSR3D.predict_answers: hot path -> prompt embeddings with the scene tokens written in and the
         object mask at their positions -> one bos embedding and a mask column of ones appended -> the `num_ans_candidates`
         answers whose first token is most probable -> the one with the smallest mean token loss ->
         data_dict['answers_id'] (B,) int64 on the device (indices into the answer list), plus 'answers_topk_ids' (B, C),
         'answers_loss' (B, C) fp32 and, with `answer_list` (the strings), 'answers'.  answer_ids / answer_mask (A, S) int64:
         the tokenised answer list, bos first, right-padded (tokenising stays outside, like all tokenising here).
-        lora: "separate" or "merged", as in `generate`."""
+        lora: "separate" or "merged", weights: "bf16" or "e4m3", as in `generate`."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if answer_list is not None and len(answer_list) != answer_ids.shape[0]:
@@ -213,7 +215,8 @@ class MSR3DFullStep(MSR3DHotPath):
         self._write_images(emb, am, ids, data_dict, train=False)
         scatter_scene_embeds_(emb, am, ids, d["scene_embeds"].detach(), d["obj_masks"], self.scene_sp_token)
         out = self.llm_model.predict_answers(emb, am, self.embed_tokens, answer_ids, answer_mask,
-                                             num_ans_candidates=num_ans_candidates, bos_id=bos_id, lora=lora)
+                                             num_ans_candidates=num_ans_candidates, bos_id=bos_id, lora=lora,
+                                             weights=weights)
         d["answers_id"] = out["answers_id"]
         d["answers_topk_ids"], d["answers_loss"] = out["topk_ids"], out["loss"]
         if answer_list is not None:

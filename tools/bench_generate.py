@@ -12,6 +12,9 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
     python tools/bench_generate.py --prompt-cache both   # a BEAM step (5 rows a prompt, a reorder in it) under the rows
                                                  #   layout and under prompt_cache="shared", alternating; bytes of either
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_generate.py --prompt-cache shared --profile 20x576
+    python tools/bench_generate.py --weights both   # the step of a base="fp8" stack on its e4m3 weights (weights="e4m3")
+                                                 #   beside the bf16 stack's, alternating; the four projection launches of a
+                                                 #   layer one by one against their streaming floors
 """
 import argparse
 import json
@@ -31,8 +34,8 @@ HIDDEN, HEADS, INTER, VOCAB = 4096, 32, 11008, 32000
 COPY_RATE = 6.29e12
 
 
-def build(layers):
-    net = LoRALlamaStack(layers, HIDDEN, HEADS, INTER, VOCAB, device="cuda")
+def build(layers, base="bf16"):
+    net = LoRALlamaStack(layers, HIDDEN, HEADS, INTER, VOCAB, device="cuda", base=base)
     gen = torch.Generator(device="cuda").manual_seed(0)
     with torch.no_grad():
         for n, b in net.named_buffers():
@@ -206,6 +209,99 @@ def prompt_cache_cells(args):
     print(json.dumps(out))
 
 
+PROJECTIONS = (("q|k|v", HIDDEN, 3 * HIDDEN), ("o", HIDDEN, HIDDEN), ("gate|up", HIDDEN, 2 * INTER), ("down", INTER, HIDDEN))
+
+
+def projection_floor_us(weights, rows, K, N):
+    """What a projection launch must stream -- the weight (codes + one f32 scale per output channel under e4m3) and the
+    activations (codes + one f32 scale per row) -- over the copy rate."""
+    nbytes = (N * K + 4 * N + rows * K + 4 * rows) if weights == "e4m3" else 2 * (N * K + rows * K)
+    return nbytes / COPY_RATE * 1e6
+
+
+def projection_launches(eng, tok, steps=5):
+    """Per-launch device time of the four projection launches of a layer (q|k|v, o, gate|up, down) and of the r-row launch
+    in front of each (under e4m3 the one that also quantises the activations), by the binding's census (events around
+    EVERY library launch, so the step itself is slower while it runs): medians over layers and `steps` steps."""
+    entry = "msr3d_fp8_skinny_lowrank" if eng.weights == "e4m3" else (
+        "msr3d_bf16_skinny_lowrank" if tok.shape[0] <= 32 else "msr3d_bf16_skinny_lowrank_wide")
+    layers = len(eng.stack.layers)
+    sink = {}
+    _lib.set_timing_sink(sink, census=True)
+    try:
+        for _ in range(steps):
+            eng.step(tok)
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_timing_sink(None)
+    r_row = "msr3d_bf16_gemm_skinny_quant" if eng.weights == "e4m3" else "msr3d_bf16_gemm_skinny"
+    out = []
+    for name in (entry, r_row):                                  # both are launched 4 a layer in the same order
+        pairs = sink[name]
+        per_step = len(pairs) // steps                           # (+ the head, last, on the bf16 entry)
+        assert per_step in (4 * layers, 4 * layers + 1), (name, per_step)
+        ts = [[] for _ in PROJECTIONS]
+        for i, (e0, e1) in enumerate(pairs):
+            j = i % per_step
+            if j < 4 * layers:
+                ts[j % 4].append(e0.elapsed_time(e1) * 1e3)
+        out.append([round(statistics.median(t), 1) for t in ts])
+    return out
+
+
+def weights_cells(args):
+    """--weights: one decode step of the bf16 stack (weights="bf16") and of a base="fp8" stack of the same shapes on its
+    e4m3 weights (weights="e4m3"), alternating repeat by repeat in one process; then, in a run of its own per engine, the
+    device time of each of the four projection launches of a layer against its streaming floor."""
+    kinds = ["bf16", "e4m3"] if args.weights == "both" else [args.weights]
+    nets = {k: build(args.layers, base="fp8" if k == "e4m3" else "bf16") for k in kinds}
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    rows_arg = args.rows if args.rows != "1,5,20,32,40,64" else "1,5,20,64"
+    grid = [(int(r), int(t)) for r in rows_arg.split(",") for t in args.lengths.split(",")]
+    if args.profile:
+        grid = [tuple(int(v) for v in args.profile.split("x"))]
+    warmup, census_steps = 3, 5
+    out = {"bench": "generate_weights", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
+           "heads": HEADS, "inter": INTER, "vocab": VOCAB, "repeats": args.repeats, "copy_rate_TBps": COPY_RATE / 1e12,
+           "weights": kinds, "projections": [p[0] for p in PROJECTIONS], "cells": []}
+    for rows, length in grid:
+        x = (torch.randn(1, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(1, length, dtype=torch.int64, device="cuda")
+        tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+        engines = []
+        for k in kinds:
+            eng = CachedDecoder(nets[k], weights=k)
+            eng.reserve(rows, args.repeats + warmup + census_steps + 28)
+            eng.prefill(x, mask)
+            eng.expand(rows)
+            engines.append(eng)
+        fns = [lambda e=e: e.step(tok) for e in engines]
+        cell = {"rows": rows, "length": length}
+        if args.profile:
+            for _ in range(20):
+                for fn in fns:
+                    fn()
+            torch.cuda.synchronize()
+            out["cells"].append(cell)
+            continue
+        stats = timed_alternating(fns, args.repeats, warmup=warmup)
+        for k, eng, st in zip(kinds, engines, stats):
+            launch, r_row = projection_launches(eng, tok, census_steps)
+            floors = [projection_floor_us(k, rows, K, N) for _, K, N in PROJECTIONS]
+            cell[k] = {"step": st, "projection_us": launch, "projection_floor_us": [round(f, 1) for f in floors],
+                       "projection_floor_fraction": [round(f / t, 3) for f, t in zip(floors, launch)], "r_row_us": r_row}
+        if len(kinds) == 2:
+            cell["e4m3_over_bf16"] = round(stats[1]["median_us"] / stats[0]["median_us"], 3)
+            cell["projection_e4m3_over_bf16"] = [round(a / b, 3) for a, b in zip(cell["e4m3"]["projection_us"],
+                                                                                cell["bf16"]["projection_us"])]
+            if "launches" not in out:
+                out["launches"] = {k: library_launches(fn) for k, fn in zip(kinds, fns)}
+        out["cells"].append(cell)
+        del engines, fns
+    print(json.dumps(out))
+
+
 def sample_cells(args):
     """--sample: one msr3d_decode_sample launch beside one msr3d_decode_select launch on the same logits (8 previous
     tokens, repetition penalty 3), and a decode step followed by either, at the two shapes decoding has: 64 rows drawing
@@ -251,10 +347,14 @@ def main():
                     help="the engine's products; both: the two steps timed in turn in one process")
     ap.add_argument("--prompt-cache", default="", choices=("", "rows", "shared", "both"),
                     help="time a beam step (5 rows a prompt, a reorder in it) under that cache layout; both: in turn")
+    ap.add_argument("--weights", default="", choices=("", "bf16", "e4m3", "both"),
+                    help="time the step on those weights (e4m3: a base='fp8' stack); both: the two stacks in turn")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
     if args.sample:
         return sample_cells(args)
+    if args.weights:
+        return weights_cells(args)
     if args.prompt_cache:
         return prompt_cache_cells(args)
     net = build(args.layers)
