@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import call, current_stream_ptr, ptr
-from .lora import PAD_R, LoRALinear, _gemm, group_inputs
+from .lora import PAD_R, LoRALinear, group_inputs
 
 
 class _RMSNormFn(torch.autograd.Function):
@@ -165,7 +165,7 @@ class ModuleProducts:
     `project(h, mods)`, the projections `mods` of the same activations h, one tensor each, and `gated(h, gate, up)`,
     silu(gate(h)) * up(h); and `head(h, lm_head)`, the logits.  This one is the module call (LoRALinear on the tiled
     GEMMs, _SwiGLUFn, FrozenLinear; differentiable): training, the full forward, `CachedDecoder.prefill` and `.score`.
-    The other is generate.SkinnyProducts, the weight-stream launches of one decode step."""
+    The others are products.py's: the decoding engine's weight sources, each also as the launches of one decode step."""
 
     @staticmethod
     def project(h, mods):
@@ -181,38 +181,11 @@ class ModuleProducts:
         return lm_head(h)
 
 
-class MergedModuleProducts:
-    """ModuleProducts on merged weights (lora="merged": `CachedDecoder.prefill` and `.score`): every projection is ONE
-    tiled product against its plane bf16(W + s B A) -- msr3d_bf16_gemm_lowrank with R = 0 -- and no r-row product.
-    planes: LoRALlamaStack.merged_weights().  Evaluation only: no autograd graph is built, and a call that would need
-    one (gradients enabled on activations that require grad) raises."""
-
-    def __init__(self, planes):
-        self.planes = planes
-
-    def project(self, h, mods):
-        if torch.is_grad_enabled() and h.requires_grad:
-            raise RuntimeError("MergedModuleProducts: merged weights are for evaluation (no backward); call under "
-                               "torch.no_grad() or use lora='separate'")
-        if not h.is_cuda:
-            raise RuntimeError("LoRALinear runs on the GPU only (no CPU fallback)")
-        x2 = h.to(torch.bfloat16).reshape(-1, h.shape[-1])
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        outs = []
-        for m in mods:
-            y = torch.empty((x2.shape[0], m.out_features), dtype=torch.bfloat16, device=h.device)
-            _gemm(x2.shape[0], m.out_features, m.in_features, 0, x2, m.in_features, self.planes[m], m.in_features, None, 0,
-                  None, 0, y, m.out_features, False, 1.0, h.device)
-            outs.append(y)
-        return outs
-
-    def gated(self, h, gate, up):
-        g, u = self.project(h, (gate, up))
-        return _SwiGLUFn.apply(g, u)
-
-    @staticmethod
-    def head(h, lm_head):
-        return lm_head(h)
+def __getattr__(name):            # (products.py imports this module: its MergedModuleProducts is re-exported lazily)
+    if name != "MergedModuleProducts":
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    from .products import MergedModuleProducts
+    return MergedModuleProducts
 
 
 def decoder_layer(layer, i, x, delta, attend, products, rows=None):

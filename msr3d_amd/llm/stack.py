@@ -195,7 +195,7 @@ class LoRALlamaStack(nn.Module):
 
     def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
                         weights="bf16", **rank_kwargs):
-        """Closed-set answer ranking on one cached copy of every prompt (msr3d_amd/llm/generate.py::rank_answers) ->
+        """Closed-set answer ranking on one cached copy of every prompt (msr3d_amd/llm/search.py::rank_answers) ->
         dict(answers_id (B,), topk_ids (B, C), loss (B, C) fp32, first_prob (B, A)).  answer_ids / answer_mask (A, S):
         the tokenised answer list, bos first, right-padded; rank_kwargs: num_ans_candidates, bos_id; lora and weights: as
         in `generate` (under weights="e4m3" the losses may move in last bits with num_ans_candidates, which sets the

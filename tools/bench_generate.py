@@ -223,8 +223,7 @@ def projection_launches(eng, tok, steps=5):
     """Per-launch device time of the four projection launches of a layer (q|k|v, o, gate|up, down) and of the r-row launch
     in front of each (under e4m3 the one that also quantises the activations), by the binding's census (events around
     EVERY library launch, so the step itself is slower while it runs): medians over layers and `steps` steps."""
-    entry = "msr3d_fp8_skinny_lowrank" if eng.weights == "e4m3" else (
-        "msr3d_bf16_skinny_lowrank" if tok.shape[0] <= 32 else "msr3d_bf16_skinny_lowrank_wide")
+    entry = eng.products.skinny.src.entry(tok.shape[0])          # (the engine's own choice for this many rows)
     layers = len(eng.stack.layers)
     sink = {}
     _lib.set_timing_sink(sink, census=True)
