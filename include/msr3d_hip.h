@@ -1264,6 +1264,41 @@ int msr3d_decode_sample(int N, int V, const void *logits, int ldl, const long lo
 int msr3d_gumbel_noise(int N, int V, long long seed, int step, int row0, float *out, int ld, msr3d_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The bookkeeping of one decoded token on the device (csrc/llm_beam.hip; two entries added within ABI v39, nothing else
+ * changed), so that a token of `generate` has
+ * nothing for the host to decide and replays from a captured graph (CachedDecoder.token_loop, `search(loop="device")`).
+ * msr3d_amd/llm/search.py states both in torch (torch_beam_advance, torch_greedy_advance); every field of the state
+ * equals the statement's bit for bit: integer and f32 arithmetic only (the adds of -1.0e9, one IEEE division by
+ * len_div[cur], comparisons), in the statement's order.
+ * msr3d_beam_advance: the state of B prompts x nb beams, updated in place --
+ *   run_scores (B, nb) f32, run_seq (B, nb, L) int64, fin_seq (B, nb, L) int64, fin_scores (B, nb) f32, fin_len (B, nb)
+ *   int64, is_fin (B, nb) bytes, heur (B) bytes, cur and done one int32 each -- from a step's val, tok (B nb, 2 nb), the
+ *   output of msr3d_decode_select with k = 2 nb, order 1 and run_scores as the beam score.  Per prompt: the 2 nb best
+ *   of its nb x 2 nb candidates; a candidate ends when its token is eos_id or cur + 1 == L; the next running beams are
+ *   the nb best of value - 1.0e9 [ended]; an ended candidate among the first nb competes for the nb kept hypotheses with
+ *   value / len_div[cur] (len_div (L) f32: (t + 1) ** length_penalty, made on the host); heur[b]: can the best running
+ *   beam, at the current length, still beat the worst kept hypothesis; done = no prompt's heur holds, or every candidate
+ *   of every prompt ended.  Also next_tok (B nb) int64 and beam_idx (B nb) int32 (global rows) for the step that
+ *   follows, and n_prev (B nb) int32 = the new cur (or NULL); then cur += 1.  work (B) int32: scratch.
+ *   THE TIE RULE: every top-k is the first k of a stable descending sort -- equal values go to the lower index (among
+ *   candidates: the lower beam, then the order msr3d_decode_select gave).  Values are never NaN.
+ *   THE OVERRUN RULE: with done != 0 at entry nothing is read or written beyond cur and done, which stay: a loop may run
+ *   tokens past the end.  cur outside 0 .. L - 1: the same.  A sequence gather moves columns 0 .. cur alone (every
+ *   later column is pad in every row), in place: whole columns through registers with a barrier between read and
+ *   write.  One workgroup per prompt and one closing workgroup; nb <= 32, 2 nb <= MSR3D_DECODE_SELECT_MAX_K.
+ * msr3d_greedy_advance: seq (N, L) int64, unfinished (N) bytes, cur, done from tok (N, ld_tok) int32 (column 0 is read):
+ *   t = unfinished[n] ? tok[n] : pad_id; seq[n][cur] = next_tok[n] = t; unfinished[n] &= t != eos_id; n_prev[n] = cur + 1
+ *   (or NULL); done = cur + 1 == L or no row unfinished; cur += 1.  The same overrun rule.  One workgroup.
+ * ------------------------------------------------------------------------- */
+int msr3d_beam_advance(int B, int nb, int L, const float *val, const int *tok, int eos_id, const float *len_div,
+                       float *run_scores, long long *run_seq, long long *fin_seq, float *fin_scores, long long *fin_len,
+                       unsigned char *is_fin, unsigned char *heur, int *cur, int *done, long long *next_tok, int *beam_idx,
+                       int *n_prev, int *work, msr3d_stream_t stream);
+int msr3d_greedy_advance(int N, int L, const int *tok, int ld_tok, int eos_id, long long pad_id, long long *seq,
+                         unsigned char *unfinished, int *cur, int *done, long long *next_tok, int *n_prev,
+                         msr3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Prefix-shared attention (csrc/llm_attn.hip; CachedDecoder.score, closed-set answer ranking): C candidate suffixes of
  * S tokens per prompt attend to ONE cached prefix of that prompt.  q, k, v (B, C, S, H, D) bf16 with row stride ld,
  * RoPE applied; k_cache, v_cache (B, Tmax, H, D) bf16, contiguous (KVCache rows); len (B) int32 in DEVICE memory,

@@ -187,6 +187,8 @@ _SIGNATURES = {
                             _c_int, _c_float, _c_int, _c_float, _c_int, _ptr, _c_int, ctypes.c_longlong, _c_int, _c_int,
                             _ptr, _ptr, _ptr, _ptr],
     "msr3d_gumbel_noise": [_c_int, _c_int, ctypes.c_longlong, _c_int, _c_int, _ptr, _c_int, _ptr],
+    "msr3d_beam_advance": [_c_int, _c_int, _c_int, _ptr, _ptr, _c_int] + [_ptr] * 15,
+    "msr3d_greedy_advance": [_c_int, _c_int, _ptr, _c_int, _c_int, ctypes.c_longlong] + [_ptr] * 7,
     "msr3d_attn_prefix_order": [_c_int],
     "msr3d_attn_prefix_fwd": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr,
                               _ptr, _c_float, _ptr, _c_int, _ptr],

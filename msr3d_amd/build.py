@@ -51,6 +51,7 @@ SOURCES = [
     ("llm_decode.hip", []),
     ("llm_decode_fp8.hip", []),
     ("llm_sample.hip", []),
+    ("llm_beam.hip", ["-ffp-contract=off"]),
     ("prompter_rows.hip", ["-ffp-contract=off"]),
     ("anchor_front.hip", ["-ffp-contract=off"]),
     ("scene_block.hip", []),

@@ -15,18 +15,21 @@ Four pieces, one module each:
                q | k | v as ONE skinny launch, rotation + cache append, decode attention, o, RMSNorm, gate | up with the
                SwiGLU epilogue, down; then the final norm and the head.  No host synchronisation inside `step`: lengths
                and positions live in device memory.  `score` runs B x C short suffixes against one cached prefix
-               (msr3d_attn_prefix_fwd, csrc/llm_attn.hip).  And the two doors, `generate` and `predict_answers`.
+               (msr3d_attn_prefix_fwd, csrc/llm_attn.hip).  `token_loop` is `search(loop="device")`'s tokens as
+               replays of captured graphs, the bookkeeping on the kernels of csrc/llm_beam.hip.  And the two doors,
+               `generate` and `predict_answers`.
 
 `max_length` counts GENERATED tokens (the prompt travels as embeddings and has no ids).  GPU only for the engine."""
 import ctypes
 import math
+import time
 
 import torch
 
 from .._lib import call, current_stream_ptr, ptr
 from .decoder import _AttentionFn, decoder_stack, rope_tables
 from .kv_cache import KVCache
-from .lora import LoRALinear, refresh_shadows
+from .lora import LoRALinear, refresh_shadows, shadows_are_fresh
 from .products import E4m3Products, MergedModuleProducts, SeparateProducts
 from .search import (_embed_fn, counter_uniform_bits, gumbel_from_bits, prompt_groups, rank_answers,  # noqa: F401
                      search, torch_sample, torch_sample_scores, torch_select)
@@ -90,6 +93,7 @@ class CachedDecoder:
         l0 = stack.layers[0]
         self.H, self.D, self.hidden = l0.num_heads, l0.head_dim, l0.hidden_size
         self.cache, self._plan, self._tables = None, (1, 256), None
+        self.capture_seconds = []         # host seconds of every graph capture of `token_loop`, in order (for benches)
         # the products of this call (merged: made at prefill / score, on the planes of that moment)
         self.products = E4m3Products() if weights == "e4m3" else (SeparateProducts() if lora == "separate" else None)
 
@@ -248,6 +252,104 @@ class CachedDecoder:
         logits = decoder_stack(st, x, attend, products)
         c.advance()
         return logits
+
+    # -- the token loop on the device ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def token_loop(self, state, logits, embed_fn, eos_id, pad_id, min_length, repetition_penalty, len_div, poll=4):
+        """`search(loop="device")`'s tokens on this engine, after prefill / expand: state (search.beam_state or
+        greedy_state, on the GPU) is advanced IN PLACE until `done`, and returned.  logits (rows, V): the prefill's,
+        one row per live row.  A token is msr3d_decode_select on the static logits buffer -> msr3d_beam_advance /
+        msr3d_greedy_advance (the state, next_tok, beam_idx, n_prev, cur, done) -> embed_fn(next_tok) -> the cache
+        reorder by the device beam_idx (beams) -> `step` -> the logits buffer: one linear chain on one stream in which
+        every operand is a static buffer or allocated by the chain itself, and nothing is decided on the host.
+        The first token runs eagerly (the warm-up: LoRA shadow tables, per-kernel attributes); from the second on a
+        token is a replay of a graph captured with torch.cuda.graph ON THE SAME STREAM, one graph per cache side --
+        a reorder gathers from side `cur` into the other, so a token captured on side 0 holds other pointers than one
+        captured on side 1: two graphs for beams, replayed in turn as the sides alternate, one for greedy search (no
+        reorder, one side).  The graphs live as long as this call (one group of `search`).  The host reads `done` every
+        `poll` tokens.
+        Bounds: the loop runs at most L = the state's sequence length tokens, whatever `done` says, and `reserve` was
+        given new_tokens >= L (checked), so the cache has a slot for every step: token i (0-based) appends at slot
+        T + i <= T + L - 1 < t_max.  Tokens run after `done` (at most poll - 1) leave the state alone (the advance
+        kernels return at once) and cost a wasted select and step within those L; msr3d_rope_kv_append and the decode
+        attention clamp `len` to the cache besides."""
+        c = self.cache
+        if c is None:
+            raise RuntimeError("CachedDecoder.token_loop before prefill")
+        beams = "run_seq" in state
+        seqs = state["run_seq"] if beams else state["seq"]
+        L, N, dev = int(seqs.shape[-1]), c.rows, logits.device
+        if seqs.numel() != N * L or tuple(logits.shape[:1]) != (N,) or not seqs.is_cuda:
+            raise ValueError("CachedDecoder.token_loop: the state and the logits must have the cache's rows, on the GPU")
+        if self._plan[1] < L:
+            raise ValueError(f"CachedDecoder.token_loop: {L} tokens do not fit the {self._plan[1]} slots reserved")
+        if int(poll) < 1:
+            raise ValueError("poll >= 1")
+        i32 = torch.int32
+        lg = logits.to(torch.bfloat16).contiguous().clone()            # THE logits buffer: every token reads and rewrites it
+        V = lg.shape[1]
+        k = 2 * state["run_scores"].shape[1] if beams else 1
+        val = torch.empty((N, k), dtype=torch.float32, device=dev)
+        tok = torch.zeros((N, k), dtype=i32, device=dev)
+        n_prev = torch.zeros((N,), dtype=i32, device=dev)
+        next_tok = torch.zeros((N,), dtype=torch.int64, device=dev)
+        cur, done = state["cur"], state["done"]
+        if beams:
+            B, nb = state["run_scores"].shape
+            beam_idx = torch.arange(N, dtype=i32, device=dev)
+            work = torch.zeros((B,), dtype=i32, device=dev)
+            is_fin, heur = state["is_fin"].view(torch.uint8), state["heur"].view(torch.uint8)
+            score = state["run_scores"]
+        else:
+            unfinished = state["unfinished"].view(torch.uint8)
+        rp, ml = ctypes.c_float(repetition_penalty), int(min_length)
+
+        def token():
+            with torch.cuda.device(dev):
+                s = current_stream_ptr(dev)
+                call("msr3d_decode_select", N, V, ptr(lg), V, ptr(seqs), L, ptr(n_prev), rp, ml, int(eos_id),
+                     ptr(score) if beams else ptr(None), 1 if beams else 0, k, ptr(val), ptr(tok), s)
+                if beams:
+                    call("msr3d_beam_advance", B, nb, L, ptr(val), ptr(tok), int(eos_id), ptr(len_div), ptr(score),
+                         ptr(seqs), ptr(state["fin_seq"]), ptr(state["fin_scores"]), ptr(state["fin_len"]), ptr(is_fin),
+                         ptr(heur), ptr(cur), ptr(done), ptr(next_tok), ptr(beam_idx), ptr(n_prev), ptr(work), s)
+                else:
+                    call("msr3d_greedy_advance", N, L, ptr(tok), k, int(eos_id), int(pad_id), ptr(seqs), ptr(unfinished),
+                         ptr(cur), ptr(done), ptr(next_tok), ptr(n_prev), s)
+            lg.copy_(self.step(embed_fn(next_tok), beam_idx if beams else None))
+
+        side = torch.cuda.Stream(device=dev)                           # the capture's stream, the eager token's as well
+        here = torch.cuda.current_stream(dev)
+        side.wait_stream(here)
+        graphs = {}
+        with torch.cuda.stream(side):
+            n = 0
+            while n < L:
+                if n == 0:
+                    token()
+                else:
+                    p = c.cur
+                    g = graphs.get(p)
+                    if g is None:
+                        g = graphs[p] = torch.cuda.CUDAGraph()
+                        # (the pairs' bf16 images are those of the prefill: no weight is written during a call, so the
+                        # graph holds no refresh of them -- what a captured TRAINING step needs and LoRALinear would add)
+                        t0 = time.perf_counter()
+                        with shadows_are_fresh(self.mods), \
+                                torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                            token()
+                        self.capture_seconds.append(time.perf_counter() - t0)
+                        if beams:
+                            c.flip()                                   # (the capture moved nothing: the data is on side p)
+                    g.replay()
+                    if beams:
+                        c.flip()
+                n += 1
+                if (n % poll == 0 or n == L) and int(done):            # (a synchronisation: every replay so far is over)
+                    break
+            side.synchronize()
+        here.wait_stream(side)
+        return state
 
     @staticmethod
     def _logits_operands(who, logits, prev, repetition_penalty, min_length, eos_id, beam_score, order, k):

@@ -147,3 +147,11 @@ class KVCache:
         for pair in ((self._pos,) if self.shared else (self._len, self._pos, self._keep)):
             torch.index_select(pair[self.cur], 0, il, out=pair[1 - self.cur])
         self.cur = 1 - self.cur
+
+    def flip(self):
+        """The other side becomes the live one.  For a captured token (CachedDecoder.token_loop): the capture of a
+        `reorder` flips `cur` without moving a byte, so the loop flips it back, and flips it after every replay of a
+        graph that holds a reorder -- `cur` then names the side the data is on, as after an eager reorder."""
+        if len(self.kv) < 2:
+            raise RuntimeError("KVCache: allocated without a second side")
+        self.cur = 1 - self.cur

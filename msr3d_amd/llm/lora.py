@@ -9,6 +9,7 @@ HBM capacity buys a transposing load path away) and fp32 masters of A / B like p
 backward are msr3d_bf16_gemm_lowrank (bf16 MFMA, fp32 accumulate) with the low-rank term as one
 extra K step, the weight gradients msr3d_lora_grad_pair (dA and dB in one launch).  GPU only
 (raises on CPU tensors)."""
+import contextlib
 import ctypes
 import math
 
@@ -153,6 +154,21 @@ def refresh_shadows(mods, capturing=False):
         call("msr3d_lora_shadows", len(jobs), ptr(tab), current_stream_ptr(dev))
     for m in stale:
         m._shadow_key = "captured" if capturing else m._pair_key()
+
+
+@contextlib.contextmanager
+def shadows_are_fresh(mods, fresh=True):
+    """Inside this block a graph capture records NO refresh of the bf16 images of `mods`' pairs: the caller vouches that
+    they are current for everything the capture will replay.  Two callers: LoRALlamaStack.logits, which has just rebuilt
+    every pair in one launch at the top of its own capture, and CachedDecoder.token_loop, whose images are the prefill's
+    (no weight is written during a decoding call).  fresh=False: a block that changes nothing (an eager forward)."""
+    for m in mods:
+        m._fresh_in_capture = bool(fresh)
+    try:
+        yield
+    finally:
+        for m in mods:
+            m._fresh_in_capture = False
 
 
 def merge_pairs(mods, planes):
@@ -338,7 +354,7 @@ class LoRALinear(nn.Module):
         nn.init.zeros_(self.lora_B.weight)
         self._wt_version = None       # `weight._version` the transposed copy was made from
         self._shadow, self._shadow_key = None, None
-        self._fresh_in_capture = False    # set by LoRALlamaStack around a captured forward (its one refresh launch)
+        self._fresh_in_capture = False    # set by `shadows_are_fresh` around a capture that needs no refresh of its own
         self._group, self._u_col = None, 0    # group_inputs(): modules reading the same tensor share one r-row product
         self._invalidations = 0               # invalidate_shadows() calls: part of the key of a stack's merged planes
 

@@ -6,7 +6,9 @@ is checked exactly against transformers -- and on the GPU with generate.CachedDe
 log-softmax or the beam score) gives the scores w a token is drawn from, `torch_sample` draws by Gumbel keys (the k
 largest w + noise = k draws without replacement), `counter_uniform_bits` is the noise's counter hash in integers.
 `CachedDecoder.sample` is all of it as one kernel (msr3d_decode_sample); `search(draw="multinomial")` draws with
-torch.multinomial instead, where transformers does, which pins `search` to transformers on the CPU."""
+torch.multinomial instead, where transformers does, which pins `search` to transformers on the CPU.
+`torch_beam_advance` / `torch_greedy_advance` state the bookkeeping of one token on a state that holds `cur` and `done`
+itself: `search(loop="device")`, whose host reads `done` every `poll` tokens (csrc/llm_beam.hip: the same as two kernels)."""
 import math
 
 import torch
@@ -157,7 +159,7 @@ def prompt_groups(B, rows_per_prompt, max_rows):
 @torch.no_grad()
 def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=2, pad_id=2, num_beams=1, max_length=256,
            min_length=1, repetition_penalty=1.0, length_penalty=1.0, do_sample=False, top_p=1.0, top_k=0, temperature=1.0,
-           num_return_sequences=1, seed=None, draw=None):
+           num_return_sequences=1, seed=None, draw=None, loop="host", poll=4):
     """-> (B n, <= max_length) int64, n = num_return_sequences, a prompt's rows adjacent: the generated tokens (the
     prompt is not part of the result).
     engine: `prefill(inputs_embeds (B, T, H), attention_mask (B, T)) -> (B, V)` logits of the last position,
@@ -191,7 +193,18 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
       beam_score, order, temperature, top_k, top_p, min_keep, k, seed, step, row0) -> (key, val, tok)` draws (one
       kernel on the GPU); without it `torch_sample_scores` + `torch_sample` do.  seed = None takes 63 bits from torch's
       CPU generator: torch.manual_seed makes a call reproducible.
-    Live rows per prompt are max(num_beams, n)."""
+    Live rows per prompt are max(num_beams, n).
+
+    loop = "host" (default): the token loop above, one synchronisation a token.  loop = "device" (greedy and beam search
+    with n <= num_beams; not sampling): the bookkeeping between two steps is `torch_greedy_advance` /
+    `torch_beam_advance` on a state that lives on the engine's device, `done` included, and the host reads `done` only
+    every `poll` tokens -- a token has nothing for the host to decide.  An engine with `token_loop(state, logits,
+    embed_fn, eos_id=, pad_id=, min_length=, repetition_penalty=, len_div=, poll=)` runs the tokens itself
+    (CachedDecoder: captured graphs, the two advances as kernels); for any other engine the statement is called step by
+    step around `engine.step`.  Either way at most max_length tokens run in all; tokens run after `done` (at most
+    poll - 1) change nothing.  Every top-k of the device loop is the first k of a STABLE descending sort (ties to the
+    lower beam, then `select`'s order), where the host loop's torch.topk leaves ties open; the length divisor is an f32
+    table applied by IEEE division."""
     nb, n_ret, L = int(num_beams), int(num_return_sequences), int(max_length)
     if nb < 1 or L < 1:
         raise ValueError("num_beams >= 1 and max_length >= 1")
@@ -205,6 +218,13 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
         raise ValueError("temperature > 0")
     if int(top_k) != top_k or top_k < 0:
         raise ValueError("top_k >= 0 (0 = off)")
+    if loop not in ("host", "device"):
+        raise ValueError(f"loop is 'host' or 'device', not {loop!r}")
+    if int(poll) != poll or poll < 1:
+        raise ValueError("poll >= 1 (tokens between two reads of `done`)")
+    if loop == "device" and do_sample:
+        raise NotImplementedError("search: loop='device' does not sample -- the draw kernel takes `step` as a launch "
+                                  "argument, which a replayed graph cannot change; use loop='host' with do_sample")
     if draw is None:
         draw = "counter" if hasattr(engine, "sample") else "multinomial"
     if draw not in ("counter", "multinomial"):
@@ -224,8 +244,12 @@ def search(engine, embed_fn, inputs_embeds, attention_mask, bos_id=None, eos_id=
     sampler = None
     if do_sample:
         sampler = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), draw=draw, seed=seed)
-    outs = [_search_group(engine, embed_fn, x[a:b], mask[a:b], bos_id, eos_id, pad_id, nb, L, min_length, repetition_penalty,
-                          length_penalty, n_ret, sampler, a * per) for a, b in groups]
+    if loop == "device":
+        outs = [_device_group(engine, embed_fn, x[a:b], mask[a:b], bos_id, eos_id, pad_id, nb, L, min_length,
+                              repetition_penalty, length_penalty, n_ret, int(poll)) for a, b in groups]
+    else:
+        outs = [_search_group(engine, embed_fn, x[a:b], mask[a:b], bos_id, eos_id, pad_id, nb, L, min_length,
+                              repetition_penalty, length_penalty, n_ret, sampler, a * per) for a, b in groups]
     if len(outs) == 1:
         return outs[0]
     width = max(o.shape[1] for o in outs)
@@ -363,6 +387,165 @@ def _search_group(engine, embed_fn, x, mask, bos_id, eos_id, pad_id, nb, L, min_
         if not bool(go_on):
             break
         logits = engine.step(embed_fn(run_seq[:, :, cur].reshape(-1)), (beam_sel + offs).reshape(-1))
+    if n_ret == 1:
+        return fin_seq[:, 0, :int(fin_len[:, 0].max())]
+    return fin_seq[:, :n_ret, :int(fin_len[:, :n_ret].max())].reshape(B * n_ret, -1)
+
+
+# ------------------------------------------------------------------------------------- the token loop on the device
+def length_divisors(L, length_penalty, device=None):
+    """-> (L) f32: d[cur] = (cur + 1) ** length_penalty, made once on the host (Python floats, rounded to f32); a
+    finished hypothesis' score is sum_logprobs / d[cur] by IEEE division."""
+    return torch.tensor([float((c + 1) ** length_penalty) for c in range(int(L))], dtype=torch.float32, device=device)
+
+
+def beam_state(B, nb, L, pad_id, device=None):
+    """The state of beam search for one group of B prompts x nb beams before its first token, as `_search_group` has it;
+    cur (tokens written) and done are one int32 each, on the device like the rest."""
+    f32, dev = torch.float32, device
+    run_scores = torch.zeros((B, nb), dtype=f32, device=dev)
+    run_scores[:, 1:] = -1.0e9
+    run_seq = torch.full((B, nb, L), int(pad_id), dtype=torch.int64, device=dev)
+    return dict(run_scores=run_scores, run_seq=run_seq, fin_seq=run_seq.clone(),
+                fin_scores=torch.full((B, nb), -1.0e9, dtype=f32, device=dev),
+                fin_len=torch.zeros((B, nb), dtype=torch.int64, device=dev),
+                is_fin=torch.zeros((B, nb), dtype=torch.bool, device=dev), heur=torch.ones((B,), dtype=torch.bool, device=dev),
+                cur=torch.zeros((1,), dtype=torch.int32, device=dev), done=torch.zeros((1,), dtype=torch.int32, device=dev))
+
+
+def greedy_state(N, L, pad_id, device=None):
+    """The state of greedy search over N rows before its first token."""
+    return dict(seq=torch.full((N, L), int(pad_id), dtype=torch.int64, device=device),
+                unfinished=torch.ones((N,), dtype=torch.bool, device=device),
+                cur=torch.zeros((1,), dtype=torch.int32, device=device), done=torch.zeros((1,), dtype=torch.int32, device=device))
+
+
+def _first_k(x, k):
+    """The indices of the k largest along dim 1 as the first k of a stable descending sort: ties to the lower index."""
+    return torch.sort(x, dim=1, descending=True, stable=True)[1][:, :k]
+
+
+def _take(t, i):                          # t (B, n, ...), i (B, m) -> (B, m, ...)
+    return torch.gather(t, 1, i.view(*i.shape, *([1] * (t.dim() - 2))).expand(*i.shape, *t.shape[2:]))
+
+
+def torch_beam_advance(state, val, tok, eos_id, len_div):
+    """THE statement of msr3d_beam_advance, device-agnostic and without a synchronisation: one token of beam search's
+    bookkeeping, what `_search_group` does between `select` and `engine.step` when it does not sample.
+    state: `beam_state`'s dict; val, tok (B nb, 2 nb): the step's candidates from `select` (order 1, run_scores as the
+    beam score); len_div: `length_divisors`.  -> (new state, next_tok (B nb) int64, beam_idx (B nb) int32, global rows);
+    the state given is not written.  Stated, not left to torch: every top-k is the first k of a stable descending sort
+    (`_first_k`); the length divisor is len_div[cur], applied by IEEE division; with `done` set the state returned equals
+    the one given, `done` included (next_tok / beam_idx are then meaningless): a loop may overrun."""
+    f32 = torch.float32
+    run_seq, heur, cur, done = state["run_seq"], state["heur"], state["cur"], state["done"]
+    B, nb, L = run_seq.shape
+    K2 = 2 * nb
+    dev = run_seq.device
+    c = cur.long().clamp(0, L - 1)                                  # (1,): the column this token is written to
+    last = (cur + 1 >= L)                                           # (1,) bool
+    div = len_div[c]                                                # (1,) f32
+    flat = val.reshape(B, nb * K2).float()
+    top_i = _first_k(flat, K2)
+    top_val = torch.gather(flat, 1, top_i)
+    src_beam = top_i // K2
+    tok_k = torch.gather(tok.reshape(B, nb * K2).long(), 1, top_i)
+    top_seq = _take(run_seq, src_beam).scatter(2, c.view(1, 1, 1).expand(B, K2, 1), tok_k[:, :, None])
+    hits = (tok_k == int(eos_id)) | last
+    # the running beams of the next step: the best candidates that did not just end
+    run_lp = top_val + hits.to(f32) * -1.0e9
+    nxt_i = _first_k(run_lp, nb)
+    n_run_seq, n_run_scores, beam_sel = _take(top_seq, nxt_i), _take(run_lp, nxt_i), _take(src_beam, nxt_i)
+    # finished hypotheses: only a candidate among the first `beams` may be kept
+    did = hits & (torch.arange(K2, device=dev) < nb)[None]
+    fl = top_val / div
+    fl = fl + (~heur)[:, None].to(f32) * -1.0e9
+    fl = fl + (~did).to(f32) * -1.0e9
+    m_scores = torch.cat([state["fin_scores"], fl], 1)
+    mi = _first_k(m_scores, nb)
+    n_fin_seq = _take(torch.cat([state["fin_seq"], top_seq], 1), mi)
+    n_fin_len = _take(torch.cat([state["fin_len"], (cur.long() + 1).expand(B, K2)], 1), mi)
+    n_is_fin = _take(torch.cat([state["is_fin"], did], 1), mi)
+    n_fin_scores = _take(m_scores, mi)
+    # can a running beam still beat the worst kept hypothesis?  (judged at the current length)
+    best_running = n_run_scores[:, :1] / div
+    worst_fin = torch.where(n_is_fin, n_fin_scores.min(1, keepdim=True)[0], torch.full_like(n_fin_scores, -1.0e9))
+    n_heur = heur & (best_running > worst_fin).any(-1)
+    go_on = n_heur.any() & ~hits.all()
+    new = dict(run_scores=n_run_scores, run_seq=n_run_seq, fin_seq=n_fin_seq, fin_scores=n_fin_scores, fin_len=n_fin_len,
+               is_fin=n_is_fin, heur=n_heur, cur=cur + 1, done=(~go_on).to(torch.int32).view(1))
+    stop = done != 0                                                # after `done`: nothing changes
+    new = {k: torch.where(stop, state[k], v) for k, v in new.items()}
+    next_tok = torch.gather(tok_k, 1, nxt_i).reshape(-1)
+    offs = (torch.arange(B, device=dev) * nb)[:, None]
+    return new, next_tok, (beam_sel + offs).reshape(-1).to(torch.int32)
+
+
+def torch_greedy_advance(state, tok, eos_id, pad_id):
+    """THE statement of msr3d_greedy_advance: one token of greedy search's bookkeeping.  state: `greedy_state`'s dict;
+    tok (N, 1): the step's `select` (order 0, k = 1).  -> (new state, next_tok (N) int64): finished rows go on as pad_id;
+    done = the last column was written or no row is unfinished; with `done` set the state returned equals the one given."""
+    seq, unfinished, cur, done = state["seq"], state["unfinished"], state["cur"], state["done"]
+    N, L = seq.shape
+    c = cur.long().clamp(0, L - 1)
+    nxt = torch.where(unfinished, tok[:, 0].long(), torch.full_like(tok[:, 0].long(), int(pad_id)))
+    n_unfinished = unfinished & (nxt != int(eos_id))
+    n_done = ((cur + 1 >= L) | ~n_unfinished.any()).to(torch.int32).view(1)
+    new = dict(seq=seq.scatter(1, c.view(1, 1).expand(N, 1), nxt[:, None]), unfinished=n_unfinished, cur=cur + 1, done=n_done)
+    stop = done != 0
+    return {k: torch.where(stop, state[k], v) for k, v in new.items()}, nxt
+
+
+def _statement_loop(engine, state, logits, embed_fn, eos_id, pad_id, min_length, repetition_penalty, len_div, poll):
+    """The device loop for an engine without `token_loop`: the statement step by step around `engine.step`.  -> state."""
+    select = getattr(engine, "select", torch_select)
+    beams = "run_seq" in state
+    L = (state["run_seq"] if beams else state["seq"]).shape[-1]
+    for n in range(L):                                     # (never more than L tokens; cur == n until `done`)
+        if beams:
+            N = state["run_scores"].numel()
+            nb = state["run_scores"].shape[1]
+            val, tok = select(logits, state["run_seq"].view(N, L)[:, :n], repetition_penalty, min_length, eos_id,
+                              state["run_scores"].view(-1), 1, 2 * nb)
+            state, nxt, beam_idx = torch_beam_advance(state, val, tok, eos_id, len_div)
+        else:
+            _, tok = select(logits, state["seq"][:, :n], repetition_penalty, min_length, eos_id, None, 0, 1)
+            state, nxt = torch_greedy_advance(state, tok, eos_id, pad_id)
+            beam_idx = None
+        if ((n + 1) % poll == 0 or n + 1 == L) and int(state["done"]):
+            break
+        if n + 1 < L:                                      # (after an unread `done` the step is wasted work, nothing else)
+            logits = engine.step(embed_fn(nxt), beam_idx)
+    return state
+
+
+def _device_group(engine, embed_fn, x, mask, bos_id, eos_id, pad_id, nb, L, min_length, repetition_penalty, length_penalty,
+                  n_ret, poll):
+    """`search(loop="device")` for one group of whole prompts that fits the engine."""
+    dev = x.device
+    if bos_id is not None:
+        x, mask = _append_bos(embed_fn, x, mask, bos_id)
+    B = x.shape[0]
+    if hasattr(engine, "reserve"):
+        engine.reserve(nb, L)
+    logits = engine.prefill(x, mask)
+    engine.expand(nb)
+    eos = -1 if eos_id is None else int(eos_id)
+    if nb == 1:
+        state, len_div = greedy_state(B, L, pad_id, dev), None
+    else:
+        state, len_div = beam_state(B, nb, L, pad_id, dev), length_divisors(L, length_penalty, dev)
+        logits = logits.repeat_interleave(nb, 0)
+    loop = getattr(engine, "token_loop", None)
+    if loop is not None:
+        state = loop(state, logits, embed_fn, eos_id=eos, pad_id=int(pad_id), min_length=int(min_length),
+                     repetition_penalty=float(repetition_penalty), len_div=len_div, poll=poll)
+    else:
+        state = _statement_loop(engine, state, logits, embed_fn, eos, int(pad_id), int(min_length),
+                                float(repetition_penalty), len_div, poll)
+    if nb == 1:
+        return state["seq"][:, :int(state["cur"])]
+    fin_seq, fin_len = state["fin_seq"], state["fin_len"]
     if n_ret == 1:
         return fin_seq[:, 0, :int(fin_len[:, 0].max())]
     return fin_seq[:, :n_ret, :int(fin_len[:, :n_ret].max())].reshape(B * n_ret, -1)

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from .. import _lib
 from .decoder import LoRALlamaDecoderLayer, ModuleProducts, causal_attention, decoder_stack
-from .lora import LoRALinear, _gemm as _lora_gemm, merge_pairs, refresh_shadows
+from .lora import LoRALinear, _gemm as _lora_gemm, merge_pairs, refresh_shadows, shadows_are_fresh
 from .losses import seq_mean_cross_entropy
 
 
@@ -158,16 +158,11 @@ class LoRALlamaStack(nn.Module):
         mods = self._pairs()
         capturing = x.is_cuda and torch.cuda.is_current_stream_capturing()
         refresh_shadows(mods, capturing)
-        for m in mods:
-            m._fresh_in_capture = capturing
-        try:
+        with shadows_are_fresh(mods, capturing):
             # the last layer's token-local half (second norm + MLP), the final norm and the head only over the positions
             # the caller reads
             return decoder_stack(self, x, causal_attention(attention_mask), ModuleProducts,
                                  slice(from_position, None) if from_position > 0 else None)
-        finally:
-            for m in mods:
-                m._fresh_in_capture = False
 
     def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
                  **search_kwargs):
@@ -188,7 +183,11 @@ class LoRALlamaStack(nn.Module):
         weights = "bf16" (default): the products read the bf16 base weights (a base="fp8" stack is refused);
         weights = "e4m3": a base="fp8" stack decodes on its own e4m3 weights, the ones its training forward multiplies
         on (CachedDecoder states what that changes: half the step's weight stream; last bits may move with the batch's
-        grouping; not with lora="merged")."""
+        grouping; not with lora="merged").
+        loop = "host" (default): one host decision and synchronisation per token; loop = "device" (greedy and beam
+        search, not sampling): a token is a replay of a captured graph, the beam bookkeeping two kernels
+        (msr3d_beam_advance / msr3d_greedy_advance), and the host reads `done` every `poll` (default 4) tokens --
+        `search` and CachedDecoder.token_loop state it; ties go to the lower index, where the host loop leaves them open."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, prompt_cache=prompt_cache,
                         weights=weights, **search_kwargs)

@@ -139,7 +139,8 @@ class MSR3DFullStep(MSR3DHotPath):
     @torch.no_grad()
     def generate(self, data_dict, num_beams=5, max_length=256, min_length=1, repetition_penalty=3.0, length_penalty=1.0,
                  max_out_len=256, bos_id=1, eos_id=2, use_nucleus_sampling=False, top_p=0.9, temperature=1.0,
-                 num_captions=1, seed=None, top_k=50, lora="separate", prompt_cache="rows", weights="bf16"):
+                 num_captions=1, seed=None, top_k=50, lora="separate", prompt_cache="rows", weights="bf16",
+                 loop="host", poll=4):
         """The reference's MSR3D.generate: hot path -> prompt embeddings with the scene tokens written in and the object
         mask at their positions (prompt only, no answer) -> one bos embedding and a mask column of ones appended -> beam
         search (or sampling) over the key / value cache (`max_length` counts generated tokens) -> id 0 mapped to 2 ->
@@ -158,7 +159,9 @@ class MSR3DFullStep(MSR3DHotPath):
         prompt_cache = "shared": the beams (or captions) of a prompt read ONE cached copy of the prompt's keys and values
         and carry only their generated tails (LoRALlamaStack.generate) -- the same tokens as the default "rows".
         weights = "e4m3": a model whose language model was built with base="fp8" decodes on its own e4m3 weights (the
-        default "bf16" refuses such a model; LoRALlamaStack.generate)."""
+        default "bf16" refuses such a model; LoRALlamaStack.generate).
+        loop = "device": greedy and beam search with the token loop as graph replays, `done` read every `poll` tokens
+        (LoRALlamaStack.generate; not with use_nucleus_sampling)."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if max_length > max_out_len:
@@ -182,7 +185,7 @@ class MSR3DFullStep(MSR3DHotPath):
                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                       do_sample=bool(use_nucleus_sampling), top_p=top_p, top_k=top_k,
                                       temperature=temperature, num_return_sequences=num_captions, seed=seed, lora=lora,
-                                      prompt_cache=prompt_cache, weights=weights)
+                                      prompt_cache=prompt_cache, weights=weights, loop=loop, poll=poll)
         out = torch.where(out == 0, torch.full_like(out, 2), out)
         pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
         d["output_tokens"] = torch.cat([out, pad], 1)

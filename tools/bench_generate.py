@@ -15,6 +15,10 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
     python tools/bench_generate.py --weights both   # the step of a base="fp8" stack on its e4m3 weights (weights="e4m3")
                                                  #   beside the bf16 stack's, alternating; the four projection launches of a
                                                  #   layer one by one against their streaming floors
+    python tools/bench_generate.py --loop both      # whole TOKENS (select + bookkeeping + step, a beam reorder in it) under
+                                                 #   search(loop="host") and loop="device" (graph replays), alternating;
+                                                 #   the capture's cost per group; the `poll` sweep; --layers-once 32 adds
+                                                 #   one cell on a 32-layer stack
 """
 import argparse
 import json
@@ -155,7 +159,7 @@ def prompt_cache_cells(args):
     emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
     gen = torch.Generator(device="cuda").manual_seed(1)
     layouts = ["rows", "shared"] if args.prompt_cache == "both" else [args.prompt_cache]
-    rows_arg = args.rows if args.rows != "1,5,20,32,40,64" else "5,20,40,64"
+    rows_arg = args.rows or "5,20,40,64"
     grid = [(int(r), int(t)) for r in rows_arg.split(",") for t in args.lengths.split(",")]
     if args.profile:
         grid = [tuple(int(v) for v in args.profile.split("x"))]
@@ -256,7 +260,7 @@ def weights_cells(args):
     nets = {k: build(args.layers, base="fp8" if k == "e4m3" else "bf16") for k in kinds}
     emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
     gen = torch.Generator(device="cuda").manual_seed(1)
-    rows_arg = args.rows if args.rows != "1,5,20,32,40,64" else "1,5,20,64"
+    rows_arg = args.rows or "1,5,20,64"
     grid = [(int(r), int(t)) for r in rows_arg.split(",") for t in args.lengths.split(",")]
     if args.profile:
         grid = [tuple(int(v) for v in args.profile.split("x"))]
@@ -334,12 +338,85 @@ def sample_cells(args):
     print(json.dumps(out))
 
 
+def loop_cells(args):
+    """--loop: whole tokens of `search` -- select, the beam bookkeeping, the step with its reorder -- under loop="host"
+    (the parent's loop: torch bookkeeping, one synchronisation a token) and loop="device" (graph replays, the advance
+    kernels, `done` read every `poll` tokens), alternating call by call in one process.  A cell's rows are whole prompts
+    of 5 beams, repetition_penalty 3.0 (1 row: greedy search, no reorder).  eos_id=None, so a call runs exactly
+    max_length tokens.  Host clock around whole `search` calls that end in a synchronise (the result is read); a token is
+    (T(SHORT + RUN tokens) - T(SHORT tokens)) / RUN: both calls hold the same prefill, eager first token and captures, the
+    difference is RUN steady-state tokens.  The capture's cost: the engine's own record (CachedDecoder.capture_seconds)."""
+    from msr3d_amd.llm.generate import _embed_fn, search
+    SHORT, RUN = 8, 32
+    loops = ["host", "device"] if args.loop == "both" else [args.loop]
+    polls = [int(p) for p in args.polls.split(",")]
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    embed = _embed_fn(emb)
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    captured = []                                                 # host seconds of every graph capture (the engine's record)
+
+    def call(net, x, mask, beams, loop, tokens, poll):
+        kw = dict(loop="device", poll=poll) if loop == "device" else {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng = CachedDecoder(net)
+        out = search(eng, embed, x, mask, eos_id=None, num_beams=beams, max_length=tokens, min_length=1,
+                     repetition_penalty=3.0, **kw)
+        out.cpu()
+        captured.extend(eng.capture_seconds)
+        return time.perf_counter() - t0
+
+    def cell(net, layers, rows, length, sweep):
+        beams = 1 if rows < BEAMS else BEAMS
+        prompts = max(1, rows // beams)
+        x = (torch.randn(prompts, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(prompts, length, dtype=torch.int64, device="cuda")
+        variants = [(lp, args.poll) for lp in loops] + ([("device", p) for p in polls if p != args.poll] if sweep else [])
+        ts = {v: ([], []) for v in variants}
+        del captured[:]
+        for rep in range(args.repeats + 1):                       # (the first repeat is the warm-up)
+            for v in variants:
+                a, b = call(net, x, mask, beams, v[0], SHORT, v[1]), call(net, x, mask, beams, v[0], SHORT + RUN, v[1])
+                if rep:
+                    ts[v][0].append(a)
+                    ts[v][1].append(b)
+        c = {"layers": layers, "live_rows": prompts * beams, "prompts": prompts, "beams": beams, "length": length,
+             "floor_us": round(step_bytes(layers, prompts * beams, length + SHORT + RUN // 2) / COPY_RATE * 1e6, 1)}
+        for v in variants:
+            per = sorted((b - a) / RUN * 1e6 for a, b in zip(*ts[v]))
+            key = v[0] if v[1] == args.poll or v[0] == "host" else f"device_poll{v[1]}"
+            c[key] = {"token_us": _stats(per), "call_short_ms": round(statistics.median(ts[v][0]) * 1e3, 2)}
+        if captured:
+            c["capture_ms_per_graph"] = round(statistics.median(captured) * 1e3, 2)
+            c["graphs_per_group"] = 2 if beams > 1 else 1
+        if "host" in c and "device" in c:
+            c["device_over_host"] = round(c["device"]["token_us"]["median_us"] / c["host"]["token_us"]["median_us"], 3)
+        return c
+
+    out = {"bench": "generate_loop", "device": torch.cuda.get_device_name(0), "hidden": HIDDEN, "heads": HEADS, "vocab": VOCAB,
+           "repeats": args.repeats, "tokens_timed": RUN, "poll": args.poll, "polls_swept": polls, "loops": loops, "cells": []}
+    rows_arg = args.rows or "1,5,20,60"
+    sweep_at = {(5, 320), (20, 320), (60, 576)}
+    if args.layers:
+        net = build(args.layers)
+        for rows in (int(r) for r in rows_arg.split(",")):
+            for length in (int(t) for t in args.lengths.split(",")):
+                out["cells"].append(cell(net, args.layers, rows, length, (rows, length) in sweep_at))
+                print(json.dumps(out["cells"][-1]), file=sys.stderr, flush=True)
+        del net
+    if args.layers_once:
+        torch.cuda.empty_cache()
+        net = build(args.layers_once)
+        out["cells"].append(cell(net, args.layers_once, 20, 320, True))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sample", action="store_true", help="time the draw kernel beside the select kernel and a step")
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--rows", default="1,5,20,32,40,64")
+    ap.add_argument("--rows", default=None, help="live rows, comma-separated (default: the mode's own grid)")
     ap.add_argument("--lengths", default="128,320,576")
     ap.add_argument("--profile", default="", help="ROWSxLENGTH: only run that decode step 20 times (for a kernel trace)")
     ap.add_argument("--lora", default="separate", choices=("separate", "merged", "both"),
@@ -348,8 +425,15 @@ def main():
                     help="time a beam step (5 rows a prompt, a reorder in it) under that cache layout; both: in turn")
     ap.add_argument("--weights", default="", choices=("", "bf16", "e4m3", "both"),
                     help="time the step on those weights (e4m3: a base='fp8' stack); both: the two stacks in turn")
+    ap.add_argument("--loop", default="", choices=("", "host", "device", "both"),
+                    help="time whole tokens of search under that token loop; both: the two loops in turn")
+    ap.add_argument("--poll", type=int, default=4, help="--loop: tokens between two reads of `done`")
+    ap.add_argument("--polls", default="1,4,8,16", help="--loop: the values of poll swept at three cells")
+    ap.add_argument("--layers-once", type=int, default=0, help="--loop: one more cell (20 x 320) on a stack this deep")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
+    if args.loop:
+        return loop_cells(args)
     if args.sample:
         return sample_cells(args)
     if args.weights:
@@ -359,7 +443,7 @@ def main():
     net = build(args.layers)
     emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
     gen = torch.Generator(device="cuda").manual_seed(1)
-    grid = [(int(r), int(t)) for r in args.rows.split(",") for t in args.lengths.split(",")]
+    grid = [(int(r), int(t)) for r in (args.rows or "1,5,20,32,40,64").split(",") for t in args.lengths.split(",")]
     if args.profile:
         grid = [tuple(int(v) for v in args.profile.split("x"))]
     out = {"bench": "generate", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
