@@ -1188,6 +1188,25 @@ int msr3d_lora_merge(int njobs, const msr3d_lora_merge_job_t *jobs_device, msr3d
  * msr3d_kv_reorder: beam search's gather dst[p][n][t] = src[p][beam_idx[n]][t], t < len[beam_idx[n]], over all
  *   `planes` (layers x {k, v}) of a (planes, N, Tmax, row_elems) bf16 cache in one launch; src != dst (two buffers
  *   ping-ponged); len describes the SOURCE rows; row_elems % 8 == 0.
+ * The e4m3 cache (four entries added within ABI v39, nothing else changed; msr3d_amd/llm/kv_cache.py states the format
+ *   in torch: torch_kv_quantize / torch_kv_dequantize).  Per (slot, head), over the D values of K and, separately, of
+ *   V: one exponent e, the smallest integer with amax 2^-e <= 448, clamped at -126 and stored as the byte b = e + 127
+ *   (e8m0: the scale is 2^(b - 127); amax == 0: b = 127), and D OCP e4m3 codes RNE(x 2^-e): an exact scaling, nothing
+ *   saturates, one rounding.  Codes live in planes shaped like the bf16 planes, one byte a value; exponents in planes
+ *   (rows, slots, lde) bytes, lde >= H (KVCache pads lde to a multiple of 16 so that msr3d_kv_reorder, called a second
+ *   time with row_elems = lde / 2, gathers them).  D = 64 or 128; code planes 16-byte aligned.
+ * msr3d_kv_quantize_e4m3: x (rows, H, D) bf16 with row stride ldx (elements) -> codes (rows, H, D), exps (rows, lde):
+ *   the statement's bytes, bit for bit.  The prefill's cache write.
+ * msr3d_rope_kv_append_e4m3: msr3d_rope_kv_append with the quantiser behind it: q gets the same bits; k is rotated and
+ *   rounded to bf16 as there, then quantised; v is quantised; codes and exponents go to slot len[n] of the planes
+ *   (N, Tmax, ...); len[n] outside 0 .. Tmax - 1: nothing is written.
+ * msr3d_attn_decode_e4m3, msr3d_attn_decode_shared_e4m3: msr3d_attn_decode / msr3d_attn_decode_shared on codes and
+ *   exponents: the same arguments with the exponent planes and lde added, the same splits, workspace and merge launch.
+ *   The output is BIT-IDENTICAL to the bf16 entry on the dequantised cache (code 2^(b - 127), a bf16 number): the
+ *   kernels are the bf16 kernels' own walk instantiated on 8-byte pieces, K's scale multiplies the reduced score and V's
+ *   the probability before the p v products, and a power of two commutes with every fp32 rounding of the chain (while
+ *   nothing is subnormal: scores and products below 2^-126 are outside the contract).  Slots >= len and masked slots
+ *   never reach a product: NaN codes (0x7f) and any exponent byte there are harmless.
  * msr3d_decode_select: per row n of logits (N, V) bf16 the top k (value, token) pairs, ties to the lower token, of
  *   order 0 (greedy):  log_softmax(processors(logits)) + beam_score[n]
  *   order 1 (beams):   processors(log_softmax(logits)) + beam_score[n]           (transformers' two decoding loops)
@@ -1253,6 +1272,21 @@ int msr3d_attn_decode_shared(int B, int G, int T, int Ttail, int H, int D, const
                              long long workspace_floats, int splits, msr3d_stream_t stream);
 int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src, void *dst, const int *beam_idx,
                      const int *len, msr3d_stream_t stream);
+int msr3d_kv_quantize_e4m3(int rows, int H, int D, const void *x, int ldx, void *codes, void *exps, int lde,
+                           msr3d_stream_t stream);
+int msr3d_rope_kv_append_e4m3(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,
+                              const int *len, const float *cos_td, const float *sin_td, int table_rows, void *k_codes,
+                              void *v_codes, void *k_exps, void *v_exps, int lde, msr3d_stream_t stream);
+int msr3d_attn_decode_e4m3(int N, int Tmax, int H, int D, const void *q, int ldq, const void *k_codes, const void *v_codes,
+                           const void *k_exps, const void *v_exps, int lde, const int *len, int len_add,
+                           const unsigned char *key_keep, float scale, void *out, int ldo, float *workspace,
+                           long long workspace_floats, msr3d_stream_t stream);
+int msr3d_attn_decode_shared_e4m3(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq,
+                                  const void *k_prompt, const void *v_prompt, const void *ke_prompt, const void *ve_prompt,
+                                  const unsigned char *prompt_keep, const void *k_tail, const void *v_tail,
+                                  const void *ke_tail, const void *ve_tail, int lde, const int *tail_len, int len_add,
+                                  float scale, void *out, int ldo, float *workspace, long long workspace_floats, int splits,
+                                  msr3d_stream_t stream);
 int msr3d_decode_select(int N, int V, const void *logits, int ldl, const long long *prev_tokens, int ld_prev,
                         const int *n_prev, float repetition_penalty, int min_length, int eos_id, const float *beam_score,
                         int order, int k, float *out_val, int *out_tok, msr3d_stream_t stream);

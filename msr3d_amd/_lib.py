@@ -181,6 +181,14 @@ _SIGNATURES = {
     "msr3d_attn_decode_shared": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr,
                                  _ptr, _c_int, _c_float, _ptr, _c_int, _ptr, ctypes.c_longlong, _c_int, _ptr],
     "msr3d_kv_reorder": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "msr3d_kv_quantize_e4m3": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr],
+    "msr3d_rope_kv_append_e4m3": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int,
+                                  _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
+    "msr3d_attn_decode_e4m3": [_c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int,
+                               _ptr, _c_float, _ptr, _c_int, _ptr, ctypes.c_longlong, _ptr],
+    "msr3d_attn_decode_shared_e4m3": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr,
+                                      _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int, _c_float, _ptr, _c_int, _ptr,
+                                      ctypes.c_longlong, _c_int, _ptr],
     "msr3d_decode_select": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,
                             _c_int, _ptr, _ptr, _ptr],
     "msr3d_decode_sample": [_c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr, _c_float, _c_int, _c_int, _ptr, _c_int,

@@ -11,6 +11,10 @@
 //     msr3d_attn_decode           one query row per (row, head) against the row's cache: a stream over K and V
 //     msr3d_attn_decode_shared    the same bits with the prompt's keys stored once per prompt: up to 8 rows a workgroup
 //     msr3d_kv_reorder            beam search's cache gather, every layer in one launch
+//     msr3d_kv_quantize_e4m3, msr3d_rope_kv_append_e4m3, msr3d_attn_decode_e4m3, msr3d_attn_decode_shared_e4m3
+//                                 the cache as e4m3 codes with one power-of-two scale per (slot, head): the prefill's
+//                                 write, the step's append, and the two attentions as instantiations of the bf16
+//                                 kernels on 8-byte pieces -- the bits of the bf16 kernels on the dequantised cache
 //     msr3d_decode_select         logits processors + log-softmax + the row's top-k candidates
 //
 // bf16 storage, fp32 accumulation.  Nothing here uses atomics: every output has one owner and partial results are
@@ -289,6 +293,101 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(int n_items, int H,
   *reinterpret_cast<uint4 *>(vc + dst + half) = *reinterpret_cast<const uint4 *>(v + src + half);
 }
 
+// ---- the e4m3 cache's quantiser -----------------------------------------------------------------------------------
+// kv_cache.torch_kv_quantize is the statement: per (slot, head) e = the smallest integer with amax 2^-e <= 448, from
+// amax's own exponent and mantissa fields (448 = 1.75 2^8: a mantissa above 1.75 takes the next exponent), clamped at
+// -126, stored biased by 127; codes = RNE_e4m3(x 2^-e), an exact scaling and one rounding.
+// `a` = amax's bf16 bits, sign cleared (for finite values the integer order is the order of the magnitudes).
+__device__ __forceinline__ int kv_biased_exponent(unsigned a) {
+  if (a == 0) return 127;
+  const int E = (int)(a >> 7), M = (int)(a & 0x7fu);
+  if (E == 0) return 1;                             // a bf16 subnormal: the clamp
+  const int e = max(E - 126 - (M <= 0x60 ? 9 : 8), -126);
+  return e + 127;
+}
+__device__ __forceinline__ unsigned amax_bits8(uint4 v) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  unsigned a = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a = max(a, max(w[i] & 0x7fffu, (w[i] >> 16) & 0x7fffu));
+  return a;
+}
+// eight bf16 values times 2^(127 - b) -> eight e4m3 codes
+__device__ __forceinline__ uint2 kv_encode8(uint4 v, int b) {
+  const float inv = __uint_as_float((unsigned)(254 - b) << 23);
+  float f[8];
+  unpack8(v, f);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, hi, true);
+  return make_uint2((unsigned)lo, (unsigned)hi);
+}
+
+// one (row, head) per D / 8 adjacent lanes, eight values a lane; amax over those lanes by shuffles (a group lies inside
+// one wave and is live or idle as a whole: n_items is a multiple of D / 8)
+template <int D>
+__global__ __launch_bounds__(256) void kv_quantize_kernel(long long n_items, int H, const u16 *__restrict__ x, int ldx,
+                                                          unsigned char *__restrict__ codes,
+                                                          unsigned char *__restrict__ exps, int lde) {
+  constexpr int LPH = D / 8;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= n_items) return;
+  const int piece = (int)(id % LPH), h = (int)((id / LPH) % H);
+  const long long row = id / ((long long)LPH * H);
+  const uint4 v = *reinterpret_cast<const uint4 *>(x + (size_t)row * ldx + (size_t)h * D + 8 * piece);
+  unsigned a = amax_bits8(v);
+#pragma unroll
+  for (int s = 1; s < LPH; s <<= 1) a = max(a, (unsigned)__shfl_xor((int)a, s));
+  const int b = kv_biased_exponent(a);
+  *reinterpret_cast<uint2 *>(codes + ((size_t)row * H + h) * D + 8 * piece) = kv_encode8(v, b);
+  if (piece == 0) exps[(size_t)row * lde + h] = (unsigned char)b;
+}
+
+// rope_kv_append_kernel with the quantiser behind it: the same thread layout (a thread owns elements [8 c, 8 c + 8) of
+// both halves of a head, D / 16 lanes a head), q rotated with the same operations, k rotated and rounded to bf16 as
+// there and then quantised, v quantised
+template <int D>
+__global__ __launch_bounds__(256) void rope_kv_append_e4m3_kernel(int n_items, int H, int Tmax, u16 *__restrict__ q,
+                                                                  const u16 *__restrict__ k, const u16 *__restrict__ v,
+                                                                  int ld, const int *__restrict__ pos,
+                                                                  const int *__restrict__ len, int table_rows,
+                                                                  const float *__restrict__ cs, const float *__restrict__ sn,
+                                                                  unsigned char *__restrict__ kc,
+                                                                  unsigned char *__restrict__ vc,
+                                                                  unsigned char *__restrict__ ke,
+                                                                  unsigned char *__restrict__ ve, int lde) {
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= n_items) return;
+  constexpr int half = D >> 1, npc = D >> 4;
+  const int c = id % npc, h = (id / npc) % H, n = id / (npc * H);
+  const int t = min(max(pos[n], 0), table_rows - 1);
+  const int slot = len[n];
+  const RopeCoef r = rope_coef(cs, sn, t, D, 8 * c);
+  const size_t src = (size_t)n * ld + (size_t)h * D + 8 * c;
+  uint4 oa, ob;
+  rope_rotate(r, *reinterpret_cast<const uint4 *>(q + src), *reinterpret_cast<const uint4 *>(q + src + half), oa, ob);
+  *reinterpret_cast<uint4 *>(q + src) = oa;
+  *reinterpret_cast<uint4 *>(q + src + half) = ob;
+  if (slot < 0 || slot >= Tmax) return;             // a full cache: nothing is written outside it (the whole head's lanes)
+  rope_rotate(r, *reinterpret_cast<const uint4 *>(k + src), *reinterpret_cast<const uint4 *>(k + src + half), oa, ob);
+  const uint4 va = *reinterpret_cast<const uint4 *>(v + src), vb = *reinterpret_cast<const uint4 *>(v + src + half);
+  unsigned ak = max(amax_bits8(oa), amax_bits8(ob)), av = max(amax_bits8(va), amax_bits8(vb));
+#pragma unroll
+  for (int s = 1; s < npc; s <<= 1) {
+    ak = max(ak, (unsigned)__shfl_xor((int)ak, s));
+    av = max(av, (unsigned)__shfl_xor((int)av, s));
+  }
+  const int bk = kv_biased_exponent(ak), bv = kv_biased_exponent(av);
+  const size_t sl = (size_t)n * Tmax + slot, dst = (sl * H + h) * D + 8 * c;
+  *reinterpret_cast<uint2 *>(kc + dst) = kv_encode8(oa, bk);
+  *reinterpret_cast<uint2 *>(kc + dst + half) = kv_encode8(ob, bk);
+  *reinterpret_cast<uint2 *>(vc + dst) = kv_encode8(va, bv);
+  *reinterpret_cast<uint2 *>(vc + dst + half) = kv_encode8(vb, bv);
+  if (c == 0) { ke[sl * lde + h] = (unsigned char)bk; ve[sl * lde + h] = (unsigned char)bv; }
+}
+
 // ---- decode attention -------------------------------------------------------------------------------------------
 // grid (H, N, S): split s of (row n, head h) takes the keys [s L / S, (s + 1) L / S) of the row's L = len[n] + len_add.
 // A key's D values are 16-byte pieces over D / 8 lanes, so a wave reads 64 / (D / 8) keys per step (4 at D = 128, 8 at
@@ -301,27 +400,87 @@ constexpr float kNegBig = -1.0e30f;
 // same bits because they call these four in the same order per row.  Every multiply-add is an explicit fmaf: left as
 // a * b + c * d, the compiler chooses per inlined copy which product it fuses (or none, where it packs two lanes), and
 // two kernels that share the expression still differ in the last bit.
-// One key (this lane's 16-byte pieces of K and V) into a lane group's online-softmax state.
-template <int LPK>
-__device__ __forceinline__ void attn_key_update(const float (&qf)[8], uint4 kv, uint4 vv, bool on, float &m, float &l,
-                                                float (&o)[8]) {
-  float kf[8], vf[8];
-  unpack8(kv, kf);
-  unpack8(vv, vf);
+// One key (this lane's eight values of K and of V) into a lane group's online-softmax state.  SCALED (the e4m3 cache):
+// the key is kf 2^a, vf 2^b with ks = 2^a, vs = 2^b given apart -- ks multiplies the reduced score and vs multiplies p
+// before the p v products (not l).  A power of two commutes with every rounding of the chain while nothing is subnormal,
+// so the state is, bit for bit, what the unscaled form makes of the multiplied-out key.
+template <int LPK, bool SCALED>
+__device__ __forceinline__ void attn_key_apply(const float (&qf)[8], const float (&kf)[8], const float (&vf)[8], float ks,
+                                               float vs, bool on, float &m, float &l, float (&o)[8]) {
   float sc = 0.f;
 #pragma unroll
   for (int e = 0; e < 8; ++e) sc = fmaf(qf[e], kf[e], sc);
 #pragma unroll
   for (int x = 1; x < LPK; x <<= 1) sc += __shfl_xor(sc, x);
+  if (SCALED) sc *= ks;
   if (on) {
     const float mn = fmaxf(m, sc);
     const float f = exp2f(m - mn), p = exp2f(sc - mn);
     l = fmaf(l, f, p);
+    const float pv = SCALED ? p * vs : p;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = fmaf(o[e], f, p * vf[e]);
+    for (int e = 0; e < 8; ++e) o[e] = fmaf(o[e], f, pv * vf[e]);
     m = mn;
   }
 }
+
+// A lane's piece of one cache slot as the decode attention reads it: eight values of K and eight of V.
+struct KvPieceBf16 {
+  uint4 k, v;
+};
+struct KvPieceE4m3 {
+  uint2 k, v;          // eight OCP e4m3 codes each
+  float ks, vs;        // the (slot, head)'s scales 2^(b - 127)
+};
+__device__ __forceinline__ void unpack8_e4m3(uint2 c, float (&f)[8]) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, true);
+  const f32x2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, false), g = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, true);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1]; f[4] = d[0]; f[5] = d[1]; f[6] = g[0]; f[7] = g[1];
+}
+__device__ __forceinline__ float e8m0_scale(unsigned char b) { return __uint_as_float((unsigned)b << 23); }
+
+template <int LPK>
+__device__ __forceinline__ void attn_key_update(const float (&qf)[8], const KvPieceBf16 &c, bool on, float &m, float &l,
+                                                float (&o)[8]) {
+  float kf[8], vf[8];
+  unpack8(c.k, kf);
+  unpack8(c.v, vf);
+  attn_key_apply<LPK, false>(qf, kf, vf, 1.f, 1.f, on, m, l, o);
+}
+template <int LPK>
+__device__ __forceinline__ void attn_key_update(const float (&qf)[8], const KvPieceE4m3 &c, bool on, float &m, float &l,
+                                                float (&o)[8]) {
+  float kf[8], vf[8];
+  unpack8_e4m3(c.k, kf);
+  unpack8_e4m3(c.v, vf);
+  attn_key_apply<LPK, true>(qf, kf, vf, c.ks, c.vs, on, m, l, o);
+}
+
+// K / V planes (rows, slots, H, D) and how a lane loads its piece of slot `sl` (an index over rows x slots) of head h.
+// e4m3: codes in the bf16 planes' shape, and the exponents (rows, slots, lde) bytes, lde >= H.
+struct KvPlanesBf16 {
+  const u16 *k, *v;
+  using Piece = KvPieceBf16;
+  static constexpr int kRowsInFlight = 4;      // attn_decode_kernel's U
+  template <int D>
+  __device__ __forceinline__ Piece load(size_t sl, int H, int h, int piece) const {
+    const size_t off = (sl * H + h) * D + 8 * piece;
+    return Piece{*reinterpret_cast<const uint4 *>(k + off), *reinterpret_cast<const uint4 *>(v + off)};
+  }
+};
+struct KvPlanesE4m3 {
+  const unsigned char *k, *v, *ke, *ve;
+  int lde;
+  using Piece = KvPieceE4m3;
+  static constexpr int kRowsInFlight = 8;
+  template <int D>
+  __device__ __forceinline__ Piece load(size_t sl, int H, int h, int piece) const {
+    const size_t off = (sl * H + h) * D + 8 * piece, eo = sl * lde + h;
+    return Piece{*reinterpret_cast<const uint2 *>(k + off), *reinterpret_cast<const uint2 *>(v + off), e8m0_scale(ke[eo]),
+                 e8m0_scale(ve[eo])};
+  }
+};
 
 // the wave's lane groups (same dims, different keys): butterfly over the group index -- every lane of a dim ends with the
 // same value, in an order fixed by the lane numbers
@@ -372,9 +531,12 @@ __device__ __forceinline__ void attn_store(int n, int h, int H, int s, int S, in
   }
 }
 
-template <int D>
+// Planes = KvPlanesBf16 or KvPlanesE4m3: the same walk -- D / 8 lanes a key, eight values a lane, the same keys per lane
+// group in the same order -- on 16-byte or 8-byte pieces.  U wave steps of loads are in flight before the first is used;
+// the e4m3 form takes twice as many, the same bytes (U changes when a key is loaded, not the order it is applied in).
+template <int D, class Planes>
 __global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const u16 *__restrict__ q, int ldq,
-                                                          const u16 *__restrict__ kc, const u16 *__restrict__ vc,
+                                                          const Planes cache,
                                                           const int *__restrict__ len, int len_add,
                                                           const unsigned char *__restrict__ keep, float scale_log2,
                                                           u16 *__restrict__ out, int ldo, float *__restrict__ part) {
@@ -394,20 +556,18 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(int Tmax, int H, const
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
   const size_t row0 = (size_t)n * Tmax;
   const unsigned char *kp = keep ? keep + row0 : nullptr;
-  constexpr int U = 4;
+  constexpr int U = Planes::kRowsInFlight;
   for (int tb = t0 + wave * KPW; tb < t1; tb += 4 * KPW * U) {
-    uint4 kv[U], vv[U];
+    typename Planes::Piece c[U];
     bool on[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = tb + u * 4 * KPW + grp;
       on[u] = t < t1 && (!kp || kp[t]);
-      const size_t off = ((row0 + (on[u] ? t : t0)) * H + h) * D + 8 * piece;     // (t0 < t1 <= Tmax here: in bounds)
-      kv[u] = *reinterpret_cast<const uint4 *>(kc + off);
-      vv[u] = *reinterpret_cast<const uint4 *>(vc + off);
+      c[u] = cache.template load<D>(row0 + (on[u] ? t : t0), H, h, piece);        // (t0 < t1 <= Tmax here: in bounds)
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) attn_key_update<LPK>(qf, kv[u], vv[u], on[u], m, l, o);
+    for (int u = 0; u < U; ++u) attn_key_update<LPK>(qf, c[u], on[u], m, l, o);
   }
   attn_group_merge<LPK>(lane, m, l, o);
   if (grp == 0) {
@@ -441,21 +601,21 @@ __global__ __launch_bounds__(D) void attn_merge_kernel(int H, int S, const float
 }
 
 // ---- decode attention, the prompt's keys stored once per prompt ---------------------------------------------------
-// The G rows of prompt b (beams) share its T prompt slots (kp, vp (B, T, H, D), pkeep (B, T)) and differ only in their
-// tails (kt, vt (B G, Ttail, H, D)); all G have the same length L = T + tail, so the split bounds and the key -> (wave,
-// lane group) assignment of attn_decode_kernel are the same for all of them.  grid (H, B ceil(G / 8), S): a workgroup
+// The G rows of prompt b (beams) share its T prompt slots (`prompt`: planes (B, T, H, D); pkeep (B, T)) and differ only in
+// their tails (`tails`: planes (B G, Ttail, H, D)); Planes as in attn_decode_kernel; all G have the same length
+// L = T + tail, so the split bounds and the key -> (wave, lane group) assignment of attn_decode_kernel are the same for
+// all of them.  grid (H, B ceil(G / 8), S): a workgroup
 // serves R <= 8 rows of one prompt (R = G up to 8 rows; above that chunks of 8, the last one partly idle), with every
 // row's online-softmax state in registers.  It walks the keys exactly as attn_decode_kernel does for ONE row -- the same
 // waves, steps and lane groups -- and applies each key to its R queries with the helpers above: per row the same
 // operations on the same values in the same order, so the bits of attn_decode_kernel on the materialised cache.  A wave
 // step (KPW keys) that lies wholly inside the prompt issues one K and one V load for all R rows; one that straddles T or
 // lies in the tail loads per row.
-template <int D, int R>
+template <int D, int R, class Planes>
 __global__ __launch_bounds__(256) void attn_decode_shared_kernel(int G, int T, int Ttail, int H, const u16 *__restrict__ q,
-                                                                 int ldq, const u16 *__restrict__ kp,
-                                                                 const u16 *__restrict__ vp,
+                                                                 int ldq, const Planes prompt,
                                                                  const unsigned char *__restrict__ pkeep,
-                                                                 const u16 *__restrict__ kt, const u16 *__restrict__ vt,
+                                                                 const Planes tails,
                                                                  const int *__restrict__ tail_len, int len_add,
                                                                  float scale_log2, u16 *__restrict__ out, int ldo,
                                                                  float *__restrict__ part) {
@@ -487,20 +647,18 @@ __global__ __launch_bounds__(256) void attn_decode_shared_kernel(int G, int T, i
   constexpr int U = 4;
   for (int tb = t0 + wave * KPW; tb < t1; tb += 4 * KPW * U) {
     if (tb + (U - 1) * 4 * KPW + KPW <= T) {          // (wave-uniform) all U steps inside the prompt: U loads in flight
-      uint4 kv[U], vv[U];
+      typename Planes::Piece c[U];
       bool on[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int t = tb + u * 4 * KPW + grp;
         on[u] = t < t1 && (!pk || pk[t]);
-        const size_t off = ((prow + (on[u] ? t : t0)) * H + h) * D + 8 * piece;   // (t0 <= tb < T here: in bounds)
-        kv[u] = *reinterpret_cast<const uint4 *>(kp + off);
-        vv[u] = *reinterpret_cast<const uint4 *>(vp + off);
+        c[u] = prompt.template load<D>(prow + (on[u] ? t : t0), H, h, piece);     // (t0 <= tb < T here: in bounds)
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv[u], vv[u], on[u], m[r], l[r], o[r]);
+        for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], c[u], on[u], m[r], l[r], o[r]);
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -508,25 +666,23 @@ __global__ __launch_bounds__(256) void attn_decode_shared_kernel(int G, int T, i
         if (ts >= t1) break;                          // (wave-uniform)
         if (ts + KPW <= T) {
           const bool on = t < t1 && (!pk || pk[t]);
-          const size_t off = ((prow + (on ? t : 0)) * H + h) * D + 8 * piece;     // (T >= 1: slot 0 exists)
-          const uint4 kv = *reinterpret_cast<const uint4 *>(kp + off), vv = *reinterpret_cast<const uint4 *>(vp + off);
+          // (T >= 1: slot 0 exists)
+          const typename Planes::Piece c = prompt.template load<D>(prow + (on ? t : 0), H, h, piece);
 #pragma unroll
-          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv, vv, on, m[r], l[r], o[r]);
+          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], c, on, m[r], l[r], o[r]);
         } else {
           // a lane's key is a prompt slot (t < T) or the row's own tail slot t - T < Ttail (t < t1 <= L); a lane
           // without a key reads prompt slot 0
           const bool tail = t >= T;
           const bool on = t < t1 && (tail || !pk || pk[t]);
-          uint4 kv[R], vv[R];
+          typename Planes::Piece c[R];
 #pragma unroll
           for (int r = 0; r < R; ++r) {
             const bool tl = on && tail;
-            const size_t off = (((tl ? trow[r] + (size_t)(t - T) : prow + (on ? t : 0))) * H + h) * D + 8 * piece;
-            kv[r] = *reinterpret_cast<const uint4 *>((tl ? kt : kp) + off);
-            vv[r] = *reinterpret_cast<const uint4 *>((tl ? vt : vp) + off);
+            c[r] = (tl ? tails : prompt).template load<D>(tl ? trow[r] + (size_t)(t - T) : prow + (on ? t : 0), H, h, piece);
           }
 #pragma unroll
-          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], kv[r], vv[r], on, m[r], l[r], o[r]);
+          for (int r = 0; r < R; ++r) attn_key_update<LPK>(qf[r], c[r], on, m[r], l[r], o[r]);
         }
       }
     }
@@ -662,23 +818,83 @@ __global__ __launch_bounds__(256) void decode_select_kernel(int V, const u16 *__
 }
 
 // the instantiation for `rows_per_wg` = min(G, 8) rows a workgroup
-template <int D>
+template <int D, class Planes>
 void attn_decode_shared_launch(int rows_per_wg, dim3 grid, hipStream_t st, int G, int T, int Ttail, int H, const u16 *q,
-                                      int ldq, const u16 *kp, const u16 *vp, const unsigned char *pkeep, const u16 *kt,
-                                      const u16 *vt, const int *tail_len, int len_add, float sl2, u16 *out, int ldo,
-                                      float *part) {
+                               int ldq, Planes prompt, const unsigned char *pkeep, Planes tails, const int *tail_len,
+                               int len_add, float sl2, u16 *out, int ldo, float *part) {
 #define MSR3D_ADS(R)                                                                                                   \
   case R:                                                                                                              \
-    attn_decode_shared_kernel<D, R><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, kp, vp, pkeep, kt, vt, tail_len,     \
-                                                          len_add, sl2, out, ldo, part);                               \
+    attn_decode_shared_kernel<D, R, Planes><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, prompt, pkeep, tails, tail_len,  \
+                                                                  len_add, sl2, out, ldo, part);                       \
     break;
   switch (rows_per_wg) {
     MSR3D_ADS(1) MSR3D_ADS(2) MSR3D_ADS(3) MSR3D_ADS(4) MSR3D_ADS(5) MSR3D_ADS(6) MSR3D_ADS(7)
     default:
-      attn_decode_shared_kernel<D, 8><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, kp, vp, pkeep, kt, vt, tail_len, len_add,
-                                                            sl2, out, ldo, part);
+      attn_decode_shared_kernel<D, 8, Planes><<<grid, 256, 0, st>>>(G, T, Ttail, H, q, ldq, prompt, pkeep, tails, tail_len,
+                                                                    len_add, sl2, out, ldo, part);
   }
 #undef MSR3D_ADS
+}
+
+// msr3d_attn_decode and msr3d_attn_decode_e4m3 behind their own checks of the planes: the same splits, workspace and
+// merge launch
+template <class Planes>
+int attn_decode_launch(int N, int Tmax, int H, int D, const void *q, int ldq, Planes cache, const int *len,
+                              int len_add, const unsigned char *key_keep, float scale, void *out, int ldo,
+                              float *workspace, long long workspace_floats, msr3d_stream_t stream) {
+  if (N > 65535 || !q || !len || !out || !al16(q)) return MSR3D_EINVAL;
+  int S = workspace ? msr3d_attn_decode_splits(N, H) : 1;
+  if (S > 1 && workspace_floats < (long long)N * H * S * (D + 2)) return MSR3D_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(H, N, S);
+  float *part = S > 1 ? workspace : nullptr;
+  if (D == 128)
+    attn_decode_kernel<128, Planes><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, cache, len, len_add, key_keep, sl2,
+                                                          (u16 *)out, ldo, part);
+  else
+    attn_decode_kernel<64, Planes><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, cache, len, len_add, key_keep, sl2,
+                                                         (u16 *)out, ldo, part);
+  if (S > 1) {
+    if (D == 128) attn_merge_kernel<128><<<dim3(H, N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
+    else attn_merge_kernel<64><<<dim3(H, N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
+  }
+  return (int)hipGetLastError();
+}
+
+// msr3d_attn_decode_shared and msr3d_attn_decode_shared_e4m3 behind their own checks of the planes
+bool attn_decode_shared_args(int B, int G, int T, int Ttail, int H, int D, int ldq, int ldo, int splits) {
+  return !(B < 0 || G <= 0 || T <= 0 || Ttail < 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) ||
+           ldo < H * D || splits < 0 || splits > MSR3D_ATTN_DECODE_MAX_SPLITS);
+}
+
+template <class Planes>
+int attn_decode_shared_launch_checked(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq,
+                                             Planes prompt, const unsigned char *prompt_keep, Planes tails,
+                                             const int *tail_len, int len_add, float scale, void *out, int ldo,
+                                             float *workspace, long long workspace_floats, int splits,
+                                             msr3d_stream_t stream) {
+  const long long N = (long long)B * G, gy = (long long)B * ((G + 7) / 8);
+  if (N > 65535 || gy > 65535 || !q || !tail_len || !out || !al16(q)) return MSR3D_EINVAL;
+  // splits 0: what msr3d_attn_decode takes for these N rows (one split without a workspace)
+  const int S = splits ? splits : (workspace ? msr3d_attn_decode_splits((int)N, H) : 1);
+  if (S > 1 && (!workspace || workspace_floats < N * H * S * (D + 2))) return MSR3D_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(H, (unsigned)gy, S);
+  float *part = S > 1 ? workspace : nullptr;
+  const int rows_per_wg = G < 8 ? G : 8;
+  if (D == 128)
+    attn_decode_shared_launch<128>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, prompt, prompt_keep, tails,
+                                   tail_len, len_add, sl2, (u16 *)out, ldo, part);
+  else
+    attn_decode_shared_launch<64>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, prompt, prompt_keep, tails,
+                                  tail_len, len_add, sl2, (u16 *)out, ldo, part);
+  if (S > 1) {
+    if (D == 128) attn_merge_kernel<128><<<dim3(H, (unsigned)N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
+    else attn_merge_kernel<64><<<dim3(H, (unsigned)N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
+  }
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -784,6 +1000,47 @@ int msr3d_rope_kv_append(int N, int H, int D, int Tmax, void *q, const void *k, 
   return (int)hipGetLastError();
 }
 
+int msr3d_kv_quantize_e4m3(int rows, int H, int D, const void *x, int ldx, void *codes, void *exps, int lde,
+                           msr3d_stream_t stream) {
+  if (rows < 0 || H <= 0 || (D != 64 && D != 128) || ldx < H * D || (ldx % 8) || lde < H) return MSR3D_EINVAL;
+  if (rows == 0) return 0;
+  if (!x || !codes || !exps || !al16(x) || !al16(codes)) return MSR3D_EINVAL;
+  const long long n = (long long)rows * H * (D / 8);
+  if ((n + 255) / 256 > 0x7fffffffLL) return MSR3D_EINVAL;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  if (D == 128)
+    kv_quantize_kernel<128><<<grid, 256, 0, st>>>(n, H, (const u16 *)x, ldx, (unsigned char *)codes, (unsigned char *)exps, lde);
+  else
+    kv_quantize_kernel<64><<<grid, 256, 0, st>>>(n, H, (const u16 *)x, ldx, (unsigned char *)codes, (unsigned char *)exps, lde);
+  return (int)hipGetLastError();
+}
+
+int msr3d_rope_kv_append_e4m3(int N, int H, int D, int Tmax, void *q, const void *k, const void *v, int ld, const int *pos,
+                              const int *len, const float *cos_td, const float *sin_td, int table_rows, void *k_codes,
+                              void *v_codes, void *k_exps, void *v_exps, int lde, msr3d_stream_t stream) {
+  if (N < 0 || H <= 0 || (D != 64 && D != 128) || Tmax <= 0 || table_rows <= 0 || ld < H * D || (ld % 8) || lde < H)
+    return MSR3D_EINVAL;
+  if (N == 0) return 0;
+  if (!q || !k || !v || !pos || !len || !cos_td || !sin_td || !k_codes || !v_codes || !k_exps || !v_exps) return MSR3D_EINVAL;
+  if (!al16(q) || !al16(k) || !al16(v) || !al16(cos_td) || !al16(sin_td) || !al16(k_codes) || !al16(v_codes))
+    return MSR3D_EINVAL;
+  const long long n = (long long)N * H * (D / 16);
+  if (n > 0x7fffffffLL) return MSR3D_EINVAL;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  using B8 = unsigned char *;
+  if (D == 128)
+    rope_kv_append_e4m3_kernel<128><<<grid, 256, 0, st>>>((int)n, H, Tmax, (u16 *)q, (const u16 *)k, (const u16 *)v, ld, pos,
+                                                          len, table_rows, cos_td, sin_td, (B8)k_codes, (B8)v_codes,
+                                                          (B8)k_exps, (B8)v_exps, lde);
+  else
+    rope_kv_append_e4m3_kernel<64><<<grid, 256, 0, st>>>((int)n, H, Tmax, (u16 *)q, (const u16 *)k, (const u16 *)v, ld, pos,
+                                                         len, table_rows, cos_td, sin_td, (B8)k_codes, (B8)v_codes,
+                                                         (B8)k_exps, (B8)v_exps, lde);
+  return (int)hipGetLastError();
+}
+
 int msr3d_attn_decode_splits(int N, int H) {
   if (N <= 0 || H <= 0) return 1;
   const long long wg = (long long)N * H;
@@ -797,61 +1054,54 @@ int msr3d_attn_decode(int N, int Tmax, int H, int D, const void *q, int ldq, con
                       float *workspace, long long workspace_floats, msr3d_stream_t stream) {
   if (N < 0 || Tmax <= 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) || ldo < H * D) return MSR3D_EINVAL;
   if (N == 0) return 0;
-  if (N > 65535 || !q || !k_cache || !v_cache || !len || !out || !al16(q) || !al16(k_cache) || !al16(v_cache))
+  if (!k_cache || !v_cache || !al16(k_cache) || !al16(v_cache)) return MSR3D_EINVAL;
+  return attn_decode_launch(N, Tmax, H, D, q, ldq, KvPlanesBf16{(const u16 *)k_cache, (const u16 *)v_cache}, len, len_add,
+                            key_keep, scale, out, ldo, workspace, workspace_floats, stream);
+}
+
+int msr3d_attn_decode_e4m3(int N, int Tmax, int H, int D, const void *q, int ldq, const void *k_codes, const void *v_codes,
+                           const void *k_exps, const void *v_exps, int lde, const int *len, int len_add,
+                           const unsigned char *key_keep, float scale, void *out, int ldo, float *workspace,
+                           long long workspace_floats, msr3d_stream_t stream) {
+  if (N < 0 || Tmax <= 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) || ldo < H * D || lde < H)
     return MSR3D_EINVAL;
-  int S = workspace ? msr3d_attn_decode_splits(N, H) : 1;
-  if (S > 1 && workspace_floats < (long long)N * H * S * (D + 2)) return MSR3D_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 grid(H, N, S);
-  float *part = S > 1 ? workspace : nullptr;
-  if (D == 128)
-    attn_decode_kernel<128><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, (const u16 *)k_cache, (const u16 *)v_cache, len,
-                                                  len_add, key_keep, sl2, (u16 *)out, ldo, part);
-  else
-    attn_decode_kernel<64><<<grid, 256, 0, st>>>(Tmax, H, (const u16 *)q, ldq, (const u16 *)k_cache, (const u16 *)v_cache, len,
-                                                 len_add, key_keep, sl2, (u16 *)out, ldo, part);
-  if (S > 1) {
-    if (D == 128) attn_merge_kernel<128><<<dim3(H, N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
-    else attn_merge_kernel<64><<<dim3(H, N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
-  }
-  return (int)hipGetLastError();
+  if (N == 0) return 0;
+  if (!k_codes || !v_codes || !k_exps || !v_exps || !al16(k_codes) || !al16(v_codes)) return MSR3D_EINVAL;
+  const KvPlanesE4m3 cache{(const unsigned char *)k_codes, (const unsigned char *)v_codes, (const unsigned char *)k_exps,
+                           (const unsigned char *)v_exps, lde};
+  return attn_decode_launch(N, Tmax, H, D, q, ldq, cache, len, len_add, key_keep, scale, out, ldo, workspace,
+                            workspace_floats, stream);
 }
 
 int msr3d_attn_decode_shared(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq, const void *k_prompt,
                              const void *v_prompt, const unsigned char *prompt_keep, const void *k_tail, const void *v_tail,
                              const int *tail_len, int len_add, float scale, void *out, int ldo, float *workspace,
                              long long workspace_floats, int splits, msr3d_stream_t stream) {
-  if (B < 0 || G <= 0 || T <= 0 || Ttail < 0 || H <= 0 || (D != 64 && D != 128) || ldq < H * D || (ldq % 8) || ldo < H * D ||
-      splits < 0 || splits > MSR3D_ATTN_DECODE_MAX_SPLITS)
-    return MSR3D_EINVAL;
+  if (!attn_decode_shared_args(B, G, T, Ttail, H, D, ldq, ldo, splits)) return MSR3D_EINVAL;
   if (B == 0) return 0;
-  const long long N = (long long)B * G, gy = (long long)B * ((G + 7) / 8);
-  if (N > 65535 || gy > 65535 || !q || !k_prompt || !v_prompt || !tail_len || !out || !al16(q) || !al16(k_prompt) ||
-      !al16(v_prompt))
-    return MSR3D_EINVAL;
+  if (!k_prompt || !v_prompt || !al16(k_prompt) || !al16(v_prompt)) return MSR3D_EINVAL;
   if (Ttail > 0 && (!k_tail || !v_tail || !al16(k_tail) || !al16(v_tail))) return MSR3D_EINVAL;
-  // splits 0: what msr3d_attn_decode takes for these N rows (one split without a workspace)
-  const int S = splits ? splits : (workspace ? msr3d_attn_decode_splits((int)N, H) : 1);
-  if (S > 1 && (!workspace || workspace_floats < N * H * S * (D + 2))) return MSR3D_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 grid(H, (unsigned)gy, S);
-  float *part = S > 1 ? workspace : nullptr;
-  const int rows_per_wg = G < 8 ? G : 8;
-  if (D == 128)
-    attn_decode_shared_launch<128>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, (const u16 *)k_prompt,
-                                   (const u16 *)v_prompt, prompt_keep, (const u16 *)k_tail, (const u16 *)v_tail, tail_len,
-                                   len_add, sl2, (u16 *)out, ldo, part);
-  else
-    attn_decode_shared_launch<64>(rows_per_wg, grid, st, G, T, Ttail, H, (const u16 *)q, ldq, (const u16 *)k_prompt,
-                                  (const u16 *)v_prompt, prompt_keep, (const u16 *)k_tail, (const u16 *)v_tail, tail_len,
-                                  len_add, sl2, (u16 *)out, ldo, part);
-  if (S > 1) {
-    if (D == 128) attn_merge_kernel<128><<<dim3(H, (unsigned)N), 128, 0, st>>>(H, S, part, (u16 *)out, ldo);
-    else attn_merge_kernel<64><<<dim3(H, (unsigned)N), 64, 0, st>>>(H, S, part, (u16 *)out, ldo);
-  }
-  return (int)hipGetLastError();
+  return attn_decode_shared_launch_checked(B, G, T, Ttail, H, D, q, ldq,
+                                           KvPlanesBf16{(const u16 *)k_prompt, (const u16 *)v_prompt}, prompt_keep,
+                                           KvPlanesBf16{(const u16 *)k_tail, (const u16 *)v_tail}, tail_len, len_add, scale,
+                                           out, ldo, workspace, workspace_floats, splits, stream);
+}
+
+int msr3d_attn_decode_shared_e4m3(int B, int G, int T, int Ttail, int H, int D, const void *q, int ldq,
+                                  const void *k_prompt, const void *v_prompt, const void *ke_prompt, const void *ve_prompt,
+                                  const unsigned char *prompt_keep, const void *k_tail, const void *v_tail,
+                                  const void *ke_tail, const void *ve_tail, int lde, const int *tail_len, int len_add,
+                                  float scale, void *out, int ldo, float *workspace, long long workspace_floats, int splits,
+                                  msr3d_stream_t stream) {
+  if (!attn_decode_shared_args(B, G, T, Ttail, H, D, ldq, ldo, splits) || lde < H) return MSR3D_EINVAL;
+  if (B == 0) return 0;
+  if (!k_prompt || !v_prompt || !ke_prompt || !ve_prompt || !al16(k_prompt) || !al16(v_prompt)) return MSR3D_EINVAL;
+  if (Ttail > 0 && (!k_tail || !v_tail || !ke_tail || !ve_tail || !al16(k_tail) || !al16(v_tail))) return MSR3D_EINVAL;
+  using B8 = const unsigned char *;
+  return attn_decode_shared_launch_checked(B, G, T, Ttail, H, D, q, ldq,
+                                           KvPlanesE4m3{(B8)k_prompt, (B8)v_prompt, (B8)ke_prompt, (B8)ve_prompt, lde},
+                                           prompt_keep, KvPlanesE4m3{(B8)k_tail, (B8)v_tail, (B8)ke_tail, (B8)ve_tail, lde},
+                                           tail_len, len_add, scale, out, ldo, workspace, workspace_floats, splits, stream);
 }
 
 int msr3d_kv_reorder(int planes, int N, int Tmax, int row_elems, const void *src, void *dst, const int *beam_idx,

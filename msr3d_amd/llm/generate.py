@@ -46,7 +46,7 @@ def _pad_tokens(x, keep, n):
 
 class CachedDecoder:
     """The decoding engine of a LoRALlamaStack (see the module docstring).  At most `max_rows` live rows (batch x beams)
-    per prefill; `search` splits a larger batch into groups of whole prompts.  THE statement of the three keywords
+    per prefill; `search` splits a larger batch into groups of whole prompts.  THE statement of the four keywords
     (LoRALlamaStack.generate and MSR3DFullStep.generate pass them on):
     weights = "bf16" (default): every product reads the bf16 base weights; a base="fp8" stack is refused.
     weights = "e4m3": a stack whose projections are all base="fp8" decodes on its own e4m3 images -- what its training
@@ -63,18 +63,29 @@ class CachedDecoder:
     than one row per prompt (beams, captions) the prompt is stored once per prompt and only the generated tail per row
     (KVCache states the layout): `expand` copies no K / V, a beam reorder gathers the tails alone, and the step's
     attention loads a prompt key once for up to 8 rows.  Every logit of every step is bit-identical to "rows".  With
-    one row per prompt there is nothing to share and the rows layout is used (`score` always sees it)."""
+    one row per prompt there is nothing to share and the rows layout is used (`score` always sees it).
+    kv = "bf16" (default) or "e4m3": the cache holds OCP e4m3 codes with one power-of-two scale per (slot, head)
+    (kv_cache.torch_kv_quantize states the format): half the bytes of the planes, of every step's attention stream and
+    of a beam reorder.  Only what is STORED is rounded, so the prefill's logits are those of "bf16"; a step's differ
+    (about 3 % rel-L2 on the test fixture) and tokens may, so "e4m3" is pinned to a statement of itself: with
+    `kv_kernels=False` the cache keeps bf16 planes on the bf16 kernels and rounds every write through the format in
+    torch, and the e4m3 kernels give that engine's logits bit for bit.  Combines with every value of the other three
+    keywords, with sampling and with prompt groups.  `score` refuses it (its cache is one prompt row read once per 64
+    suffix rows: nothing to gain), so `predict_answers` has no such keyword."""
 
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
-    def __init__(self, stack, lora="separate", prompt_cache="rows", weights="bf16"):
+    def __init__(self, stack, lora="separate", prompt_cache="rows", weights="bf16", kv="bf16", kv_kernels=True):
         if lora not in ("separate", "merged"):
             raise ValueError(f"lora is 'separate' or 'merged', not {lora!r}")
         if prompt_cache not in ("rows", "shared"):
             raise ValueError(f"prompt_cache is 'rows' or 'shared', not {prompt_cache!r}")
         if weights not in ("bf16", "e4m3"):
             raise ValueError(f"weights is 'bf16' or 'e4m3', not {weights!r}")
+        if kv not in ("bf16", "e4m3"):
+            raise ValueError(f"kv is 'bf16' or 'e4m3', not {kv!r}")
         self.stack, self.lora, self.prompt_cache, self.weights = stack, lora, prompt_cache, weights
+        self.kv, self.kv_kernels = kv, bool(kv_kernels)
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
         if weights == "bf16":
             if any(m.base == "fp8" for m in self.mods):
@@ -138,10 +149,12 @@ class CachedDecoder:
             raise ValueError("CachedDecoder.prefill: positions is 'mask' or 'arange'")
         t_max = T + new_tokens
         # the layout, decided here and nowhere else (one row a prompt: nothing to share)
+        fmt = dict(dtype=self.kv, kernels=self.kv_kernels)
         if self.prompt_cache == "shared" and beams > 1 and new_tokens > 0:
-            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=True, layout="shared", prompts=B, t_prompt=T)
+            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=True, layout="shared", prompts=B, t_prompt=T,
+                            **fmt)
         else:
-            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1)
+            cache = KVCache(len(st.layers), B * beams, t_max, H, D, dev, pingpong=beams > 1, **fmt)
         self.cache = cache
         rows = max(t_max, Tp)
         cos, sin = rope_tables(rows, D, st.layers[0].theta, dev)
@@ -181,6 +194,8 @@ class CachedDecoder:
         except under weights="e4m3", where a chunk of fewer than 128 rows multiplies on another kernel than a larger one
         and may differ in last bits)."""
         st, c = self.stack, self.cache
+        if self.kv != "bf16":
+            raise ValueError("CachedDecoder.score reads a bf16 cache (msr3d_attn_prefix_fwd); kv='e4m3' is for generate")
         if c is None:
             raise RuntimeError("CachedDecoder.score before prefill")
         if self._plan[0] != 1:
@@ -414,11 +429,11 @@ class CachedDecoder:
 
 @torch.no_grad()
 def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
-             **search_kwargs):
+             kv="bf16", **search_kwargs):
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); lora,
-    prompt_cache, weights: as CachedDecoder states them; search_kwargs: everything `search` takes."""
-    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache, weights=weights), _embed_fn(embed_tokens),
-                  inputs_embeds, attention_mask, **search_kwargs)
+    prompt_cache, weights, kv: as CachedDecoder states them; search_kwargs: everything `search` takes."""
+    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache, weights=weights, kv=kv),
+                  _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
 
 
 @torch.no_grad()

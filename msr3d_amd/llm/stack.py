@@ -165,7 +165,7 @@ class LoRALlamaStack(nn.Module):
                                  slice(from_position, None) if from_position > 0 else None)
 
     def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
-                 **search_kwargs):
+                 kv="bf16", **search_kwargs):
         """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
         -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
         (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
@@ -184,13 +184,17 @@ class LoRALlamaStack(nn.Module):
         weights = "e4m3": a base="fp8" stack decodes on its own e4m3 weights, the ones its training forward multiplies
         on (CachedDecoder states what that changes: half the step's weight stream; last bits may move with the batch's
         grouping; not with lora="merged").
+        kv = "bf16" (default): the key / value cache holds what the projections wrote;
+        kv = "e4m3": it holds e4m3 codes with a power-of-two scale per (slot, head) -- half the cache, half the bytes
+        every step's attention and every beam reorder move; the logits move by about 3 % rel-L2 (CachedDecoder and
+        kv_cache.torch_kv_quantize state the format and what it is pinned to).  With every value of the other keywords.
         loop = "host" (default): one host decision and synchronisation per token; loop = "device" (greedy and beam
         search, not sampling): a token is a replay of a captured graph, the beam bookkeeping two kernels
         (msr3d_beam_advance / msr3d_greedy_advance), and the host reads `done` every `poll` (default 4) tokens --
         `search` and CachedDecoder.token_loop state it; ties go to the lower index, where the host loop leaves them open."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, prompt_cache=prompt_cache,
-                        weights=weights, **search_kwargs)
+                        weights=weights, kv=kv, **search_kwargs)
 
     def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
                         weights="bf16", **rank_kwargs):

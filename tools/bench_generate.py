@@ -15,6 +15,9 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
     python tools/bench_generate.py --weights both   # the step of a base="fp8" stack on its e4m3 weights (weights="e4m3")
                                                  #   beside the bf16 stack's, alternating; the four projection launches of a
                                                  #   layer one by one against their streaming floors
+    python tools/bench_generate.py --kv both [--prompt-cache shared] [--lora merged]   # the step on the bf16 and on the
+                                                 #   e4m3 key / value cache (kv="e4m3"), alternating; the attention, append
+                                                 #   and reorder launches of each against the attention's streaming floor
     python tools/bench_generate.py --loop both      # whole TOKENS (select + bookkeeping + step, a beam reorder in it) under
                                                  #   search(loop="host") and loop="device" (graph replays), alternating;
                                                  #   the capture's cost per group; the `poll` sweep; --layers-once 32 adds
@@ -305,6 +308,98 @@ def weights_cells(args):
     print(json.dumps(out))
 
 
+def kv_launches(eng, fn, steps=5):
+    """Per-launch device time of the cache's launches in a step, by the binding's census (events around EVERY library
+    launch): the attention and the append as medians over layers and `steps` steps, the reorder as the median over steps
+    of a step's sum (one launch under bf16, two -- codes, exponents -- under e4m3)."""
+    e4 = "_e4m3" if eng.kv == "e4m3" else ""
+    attn = ("msr3d_attn_decode_shared" if eng.cache.shared else "msr3d_attn_decode") + e4
+    sink = {}
+    _lib.set_timing_sink(sink, census=True)
+    try:
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+    finally:
+        _lib.set_timing_sink(None)
+    us = lambda pairs: [e0.elapsed_time(e1) * 1e3 for e0, e1 in pairs]     # noqa: E731
+    out = {"attention_us": round(statistics.median(us(sink[attn])), 1),
+           "append_us": round(statistics.median(us(sink["msr3d_rope_kv_append" + e4])), 1)}
+    if "msr3d_kv_reorder" in sink:
+        t = us(sink["msr3d_kv_reorder"])
+        per = len(t) // steps
+        out["reorder_us"] = round(statistics.median([sum(t[i * per:(i + 1) * per]) for i in range(steps)]), 1)
+        out["reorder_launches"] = per
+    return out
+
+
+def kv_cells(args):
+    """--kv: one decode step on the bf16 cache and on the e4m3 cache (kv="e4m3"), alternating repeat by repeat in one
+    process -- 1 row: one prompt, no beams; otherwise 5 rows a prompt with a beam reorder in the step (a row count that is
+    no multiple of 5 runs as the whole prompts that fit: 64 -> 60) -- under --prompt-cache rows (default) or shared and
+    --lora separate (default) or merged; then, in a run of its own per engine, the attention, append and reorder launches.
+    Floors: the attention's K / V bytes of ONE layer (codes + exponent records under e4m3) over the copy rate."""
+    kinds = ["bf16", "e4m3"] if args.kv == "both" else [args.kv]
+    layout = args.prompt_cache or "rows"
+    lora = "merged" if args.lora == "merged" else "separate"
+    net = build(args.layers)
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    grid = [(int(r), int(t)) for r in (args.rows or "1,5,20,64").split(",") for t in args.lengths.split(",")]
+    if args.profile:
+        grid = [tuple(int(v) for v in args.profile.split("x"))]
+    warmup, census_steps = 3, 5
+    out = {"bench": "generate_kv", "device": torch.cuda.get_device_name(0), "layers": args.layers, "hidden": HIDDEN,
+           "heads": HEADS, "repeats": args.repeats, "copy_rate_TBps": COPY_RATE / 1e12, "kv": kinds, "prompt_cache": layout,
+           "lora": lora, "cells": []}
+    D = HIDDEN // HEADS
+    for want, length in grid:
+        beams = 1 if want < BEAMS else BEAMS
+        prompts = max(1, want // beams)
+        rows = prompts * beams
+        x = (torch.randn(prompts, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(prompts, length, dtype=torch.int64, device="cuda")
+        tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+        g = torch.arange(rows, device="cuda")
+        beam_idx = (g // beams) * beams + (g % beams + 1) % beams if beams > 1 else None
+        engines = []
+        for k in kinds:
+            eng = CachedDecoder(net, lora=lora, prompt_cache=layout, kv=k)
+            eng.reserve(beams, args.repeats + warmup + census_steps + 28)
+            eng.prefill(x, mask)
+            eng.expand(beams)
+            engines.append(eng)
+        fns = [lambda e=e: e.step(tok, beam_idx) for e in engines]
+        cell = {"live_rows": rows, "prompts": prompts, "length": length, "shared": engines[0].cache.shared,
+                "splits": _lib.load().msr3d_attn_decode_splits(rows, HEADS)}
+        if args.profile:
+            for _ in range(20):
+                for fn in fns:
+                    fn()
+            torch.cuda.synchronize()
+            out["cells"].append(cell)
+            continue
+        stats = timed_alternating(fns, args.repeats, warmup=warmup)
+        tail = warmup + args.repeats + census_steps // 2               # (the census runs after the timed repeats)
+        slots = (prompts * length + rows * tail) if engines[0].cache.shared else rows * (length + tail)
+        for k, eng, fn, st in zip(kinds, engines, fns, stats):
+            slot_bytes = 2 * (HEADS * D + eng.cache.exp_pad) if k == "e4m3" else 2 * 2 * HEADS * D     # K and V of a slot
+            floor = slots * slot_bytes / COPY_RATE * 1e6
+            cell[k] = {"step": st, "cache_bytes": eng.cache.nbytes, **kv_launches(eng, fn, census_steps),
+                       "attention_floor_us": round(floor, 1)}
+            cell[k]["attention_floor_fraction"] = round(floor / cell[k]["attention_us"], 3)
+        if len(kinds) == 2:
+            a, b = cell["bf16"], cell["e4m3"]
+            cell["e4m3_over_bf16"] = {key: round(b[key] / a[key], 3) for key in ("attention_us", "append_us", "reorder_us",
+                                                                                  "cache_bytes") if key in a}
+            cell["e4m3_over_bf16"]["step"] = round(stats[1]["median_us"] / stats[0]["median_us"], 3)
+            if "launches" not in out and beams > 1:
+                out["launches"] = {k: library_launches(fn) for k, fn in zip(kinds, fns)}
+        out["cells"].append(cell)
+        del engines, fns
+    print(json.dumps(out))
+
+
 def sample_cells(args):
     """--sample: one msr3d_decode_sample launch beside one msr3d_decode_select launch on the same logits (8 previous
     tokens, repetition penalty 3), and a decode step followed by either, at the two shapes decoding has: 64 rows drawing
@@ -425,6 +520,9 @@ def main():
                     help="time a beam step (5 rows a prompt, a reorder in it) under that cache layout; both: in turn")
     ap.add_argument("--weights", default="", choices=("", "bf16", "e4m3", "both"),
                     help="time the step on those weights (e4m3: a base='fp8' stack); both: the two stacks in turn")
+    ap.add_argument("--kv", default="", choices=("", "bf16", "e4m3", "both"),
+                    help="time the step on that key / value cache (with --prompt-cache rows|shared, --lora separate|merged); "
+                         "both: the two caches in turn, and the attention, append and reorder launches of each")
     ap.add_argument("--loop", default="", choices=("", "host", "device", "both"),
                     help="time whole tokens of search under that token loop; both: the two loops in turn")
     ap.add_argument("--poll", type=int, default=4, help="--loop: tokens between two reads of `done`")
@@ -436,6 +534,8 @@ def main():
         return loop_cells(args)
     if args.sample:
         return sample_cells(args)
+    if args.kv:
+        return kv_cells(args)
     if args.weights:
         return weights_cells(args)
     if args.prompt_cache:
