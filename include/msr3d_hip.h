@@ -1022,7 +1022,7 @@ int msr3d_bf16_gemm_batched(int outer, int inner, int M, int N, int K, const voi
  * arithmetic; transformers.models.llama.modeling_llama: LlamaRMSNorm, apply_rotary_pos_emb, LlamaMLP;
  * /root/reference/model/msr3d/msr3d.py:409-415 runs them under bf16 autocast):
  *   rmsnorm_fwd   s = x (+ delta) [-> sum_out]; y = w * bf16(s * rsqrt(mean(s^2) + eps)); rstd (M) f32.
- *                 D in {512, 1024, 2048, 4096, 5120, 8192}.
+ *                 D in {512, 1024, 1536 (forward only), 2048, 4096, 5120, 8192}.
  *   rmsnorm_bwd   dx = rstd * (dy w - xh mean(dy w xh)) (+ dres), xh = s rstd   (w is frozen: no dw)
  *   rope_inplace  x (B, T, H, D) bf16 *= rotation by (cos, sin) (T, D) f32; transpose != 0: the backward
  *   swiglu_fwd / bwd     h = silu(gate) * up and its two gradients; n % 8 == 0 */
@@ -1149,6 +1149,24 @@ int msr3d_lora_merge(int njobs, const msr3d_lora_merge_job_t *jobs_device, msr3d
  *   or four 16-row activation tiles per workgroup, with 32 rows of W per workgroup wherever that leaves >= 256
  *   workgroups.  A row of C is computed from that row of P and P2 alone; rows >= M are read clamped and never stored.
  *   msr3d_bf16_skinny_lowrank itself still refuses M > MSR3D_SKINNY_MAX_M.
+ * msr3d_bf16_skinny_fused (added within ABI v39, nothing else changed): msr3d_bf16_skinny_lowrank_wide's argument list
+ *   (0 <= M <= MSR3D_SKINNY_WIDE_MAX_M in this one entry; R must be 0 and P2 is not read) with the launches that stand
+ *   around the product in a decode step folded into it, each BIT-IDENTICAL to the chain it replaces (the kernels share
+ *   the device functions of csrc/llm_rowmath.h; the sums themselves are untouched).  All three off: the plain launch.
+ *   norm_w (K) bf16 and eps, or NULL -- the prologue: the product reads RMSNorm(P) norm_w, i.e. what msr3d_rmsnorm_fwd(M,
+ *     K, P, NULL, norm_w, eps, ...) writes as y; every workgroup computes its rows' rstd before its K loop.  K % 512 == 0,
+ *     K <= 8192 (the norm's domain), norm_w 16-byte aligned.
+ *   res (M, N_0) bf16 with row stride ldres >= N_0, or NULL -- the residual epilogue: C_0 = bf16(res + bf16(sum)), what
+ *     msr3d_rmsnorm_fwd(x = res, delta = C_0) stores as sum_out.  njobs == 1, no swiglu, no rotation; res != C_0 (the
+ *     operand is never overwritten) and 16-byte aligned.
+ *   H > 0 -- the rotation + append epilogue, msr3d_rope_kv_append(M, H, D, Tmax, q, k, v, ., pos, len, cos_td, sin_td,
+ *     table_rows, k_plane, v_plane) on the three jobs q, k, v (njobs == 3, every N_j == H D, D % 32 == 0, no swiglu):
+ *     C_0 receives q rotated by pos[n] (clamped to 0 .. table_rows - 1); k rotated and v go to slot len[n] of k_plane /
+ *     v_plane (M, Tmax, H, D) bf16 alone -- C_1 and C_2 are not written and may be NULL; len[n] outside 0 .. Tmax - 1
+ *     writes nothing to the planes and still rotates q.  A 16-row tile of W is eight columns of one head and their eight
+ *     partners D / 2 further on, so a rotary pair meets in one workgroup under the plain entry's tile rule.  H == 0: off,
+ *     the arguments behind it are not read.  cos_td, sin_td and the planes 16-byte aligned.
+ *   The SwiGLU epilogue combines with the prologue only.  Anything else: MSR3D_EINVAL.
  * msr3d_fp8_skinny_lowrank (csrc/llm_decode_fp8.hip; added within ABI v39, nothing else changed): the same product on
  *   OCP e4m3 weights, half the stream: C_j (M, N_j) bf16 = diag(sp) (Pq Wq_j^T) diag(sw_j) + P2 B2_j^T for njobs <= 3
  *   weights.  Pq (M, K) e4m3 codes and sp (M) f32 row scales: exactly what msr3d_bf16_gemm_skinny_quant writes; Wq_j
@@ -1248,6 +1266,11 @@ int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const
                               const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
 int msr3d_bf16_skinny_lowrank_wide(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
                                    const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream);
+int msr3d_bf16_skinny_fused(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                            const msr3d_skinny_job_t *jobs, int swiglu, const void *norm_w, float eps, const void *res,
+                            int ldres, int H, int D, const int *pos, const int *len, const float *cos_td,
+                            const float *sin_td, int table_rows, void *k_plane, void *v_plane, int Tmax,
+                            msr3d_stream_t stream);
 typedef struct {
   const void *Wq; int ldw;     /* (N, K) e4m3 codes */
   const float *sw;             /* (N) f32: one scale per output channel */

@@ -170,6 +170,9 @@ _SIGNATURES = {
                                   _c_int, _ptr],
     "msr3d_bf16_skinny_lowrank_wide": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int,
                                        ctypes.POINTER(SkinnyJob), _c_int, _ptr],
+    "msr3d_bf16_skinny_fused": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _c_int, ctypes.POINTER(SkinnyJob),
+                                _c_int, _ptr, _c_float, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr,
+                                _ptr, _c_int, _ptr],
     "msr3d_fp8_skinny_lowrank": [_c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int,
                                  ctypes.POINTER(Fp8SkinnyJob), _c_int, _ptr],
     "msr3d_rope_positions": [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],

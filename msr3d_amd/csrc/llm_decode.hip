@@ -4,6 +4,8 @@
 //
 //     msr3d_bf16_skinny_lowrank   C (M <= 32, N) = P W^T + P2 B2^T      every projection and the head: a weight stream
 //     msr3d_bf16_skinny_lowrank_wide   the same for M <= 64: three and four activation tiles a workgroup
+//     msr3d_bf16_skinny_fused     the same product (R = 0) with the step's norm as a prologue, its residual addition or its
+//                                 rotation + cache append as an epilogue: the bits of the launches it replaces
 //     msr3d_fp8_skinny_lowrank    the same product on e4m3 weights and row-quantised activations, M <= 64, half the
 //                                 stream (llm_decode_fp8.hip: this file's skinny_kernel on the MX fp8 instruction)
 //     msr3d_rope_kv_append        rotate q, k by the row's own position, write k, v into cache slot len[n]
@@ -27,31 +29,15 @@
 #include <cstdint>
 
 #include "../../include/msr3d_hip.h"
+#include "llm_rowmath.h"
 
 namespace {
 
-using u16 = unsigned short;
+using namespace msr3d::llm;          // u16, bf2f, f2bf, unpack8, pack8, the RMSNorm row arithmetic, rope_pair
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {
-  unsigned u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ void unpack8(uint4 v, float (&f)[8]) {
-  const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  unsigned w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = (unsigned)f2bf(f[2 * i]) | ((unsigned)f2bf(f[2 * i + 1]) << 16);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // a 16-byte piece of a weight: read once per call and never again -- non-temporal, so the stream does not push the
@@ -88,10 +74,47 @@ struct SkinnyJobs {
   int njobs;
 };
 
-template <int MT, int TN, bool SWIGLU>
-__global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const u16 *__restrict__ P, int ldp,
-                                                     const u16 *__restrict__ P2, int ldp2, SkinnyJobs jobs) {
+// What msr3d_bf16_skinny_fused adds to the product (step="fused", generate.CachedDecoder): the launches around it in a
+// decode step, restated as a prologue on its activation operand and as epilogues on its finished sums -- each through the
+// device functions of the launch it replaces (llm_rowmath.h), so the bits of the split chain.  Nothing changes the sums:
+// every output element is still the four waves' K quarters added in wave order.
+//   NORM  (q | k | v, gate | up, the head)  the operand is RMSNorm(P) nw: rmsnorm_fwd_kernel's rstd per row, computed by
+//         every workgroup for its M rows before the K loop (one wave a row, waves taking rows w, w + 4, ...), and its two
+//         roundings applied to each 16-byte piece as it enters the matrix pipe.  K = hidden: K % 512 == 0, K <= 8192.
+//   RES   (o, down)  C = bf16(res + bf16(sum)): the addition rmsnorm_fwd_kernel does in front of the next norm.
+//   ROPE  (q | k | v on a bf16 cache)  rope_kv_append_kernel: a 16-row tile of W is eight columns [i0, i0 + 8) of ONE head
+//         and their eight partners [i0 + D / 2, ...), so both halves of each rotary pair meet in one workgroup under the
+//         plain entry's own tile rule (pairing the 16-column tiles c and c + D / 2 instead forces two tiles a workgroup:
+//         384 workgroups for Vicuna's q | k | v where the plain launch has 768, 1.5 a CU, and the launch measured 10 us
+//         slower for it); q rotated -> C[0], k rotated and v -> slot len[n] of the planes (the same guard: a slot outside
+//         0 .. Tmax - 1 writes nothing to the cache, q is still rotated).
+struct SkinnyFused {
+  const u16 *nw;                 // NORM: the norm weight (K), eps, 1 / K as a float
+  float eps, inv_k;
+  const u16 *res;                // RES: the residual operand (M, N), row stride ldres
+  int ldres;
+  int H, D, table_rows, Tmax;    // ROPE: heads x head size = every job's N; cos / sin (table_rows, D); planes (M, Tmax, H, D)
+  const int *pos, *len;
+  const float *cs, *sn;
+  u16 *kc, *vc;
+};
+
+// one 16-byte piece of the activations as the matrix pipe reads it under NORM: rmsnorm_fwd_kernel's y for these elements
+__device__ __forceinline__ u32x4 norm_operand(u32x4 x, u32x4 nw, float rstd) {
+  float s[8], gf[8];
+  unpack8(__builtin_bit_cast(uint4, x), s);
+  unpack8(__builtin_bit_cast(uint4, nw), gf);
+  return __builtin_bit_cast(u32x4, rms_scale8(s, gf, rstd));
+}
+
+// THE product: skinny_kernel (the plain entries) and skinny_fused_kernel are this body
+template <int MT, int TN, bool SWIGLU, bool NORM, bool RES, bool ROPE>
+__device__ __forceinline__ void skinny_body(int M, int K, int R, const u16 *__restrict__ P, int ldp,
+                                            const u16 *__restrict__ P2, int ldp2, const SkinnyJobs &jobs,
+                                            const SkinnyFused &fz) {
+  static_assert(!(ROPE && (SWIGLU || RES)) && !(SWIGLU && RES), "epilogues exclude each other");
   __shared__ float red[4][MT * TN][64][4];
+  __shared__ float rstd_s[NORM ? MT * 16 : 1];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r16 = lane & 15, g = lane >> 4;
   int tile = blockIdx.x, job = 0;
@@ -99,12 +122,17 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
     while (job + 1 < jobs.njobs && tile >= jobs.tiles[job]) { tile -= jobs.tiles[job]; ++job; }
   }
   // SWIGLU: job 0 = gate, job 1 = up, the workgroup takes the SAME 16 rows of both (TN == 2 is the job index)
+  // ROPE: tile tt = (head, c), c < D / 16: the rows [8 c, 8 c + 8) of the head's two halves
+  const int rope_tiles = ROPE ? fz.D >> 4 : 1, half = ROPE ? fz.D >> 1 : 0;
   const u16 *wrow[TN];
   const u16 *brow[TN];
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
     const int j = SWIGLU ? t : job;
-    const int n = SWIGLU ? tile * 16 + r16 : (tile * TN + t) * 16 + r16;
+    const int tt = tile * TN + t;
+    const int n = SWIGLU ? tile * 16 + r16
+                         : (ROPE ? (tt / rope_tiles) * fz.D + (tt % rope_tiles) * 8 + (r16 & 7) + (r16 >> 3) * half
+                                 : tt * 16 + r16);
     wrow[t] = jobs.W[j] + (size_t)n * jobs.ldw[j] + 8 * g;
     brow[t] = jobs.B2[j] ? jobs.B2[j] + (size_t)n * jobs.ldb2[j] + 8 * g : nullptr;
   }
@@ -122,7 +150,8 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
 
   const int chunks = K >> 7;
   const int c0 = (chunks * wave) >> 2, c1 = (chunks * (wave + 1)) >> 2;
-  u32x4 w[TN][4], a[MT][4];
+  u32x4 w[TN][4], a[MT][4], nw[NORM ? 4 : 1];
+  const u16 *nrow = NORM ? fz.nw + 8 * g : nullptr;   // the norm weight's pieces travel with the activations'
   if (c0 < c1) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -130,10 +159,39 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
       for (int t = 0; t < TN; ++t) w[t][i] = load_stream(wrow[t] + (size_t)c0 * 128 + 32 * i);
 #pragma unroll
       for (int m = 0; m < MT; ++m) a[m][i] = load_keep(prow[m] + (size_t)c0 * 128 + 32 * i);
+      if (NORM) nw[i] = load_keep(nrow + (size_t)c0 * 128 + 32 * i);
     }
   }
+  float rstd[MT];
+  if (NORM) {
+    // rmsnorm_fwd_kernel's row walk, under the first chunk's weight loads: lane l owns the 16-byte vectors v 64 + l, the
+    // sum of squares grows in (v, e) order (eight vectors of loads in flight change when a vector arrives, not the order)
+    const int V = K >> 9;
+    for (int row = wave; row < M; row += 4) {         // (wave-uniform)
+      const u16 *xr = P + (size_t)row * ldp + 8 * lane;
+      float ss = 0.f;
+      for (int v0 = 0; v0 < V; v0 += 8) {
+        uint4 x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (v0 + u < V) x[u] = *reinterpret_cast<const uint4 *>(xr + (size_t)(v0 + u) * 512);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (v0 + u < V) {
+            float s[8];
+            unpack8(x[u], s);
+            ss = rms_sumsq8(s, ss);
+          }
+      }
+      const float r = rms_rstd(ss, fz.inv_k, fz.eps);
+      if (lane == 0) rstd_s[row] = r;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MT; ++m) rstd[m] = rstd_s[min(m * 16 + r16, M - 1)];
+  }
   for (int c = c0; c < c1; ++c) {
-    u32x4 wn[TN][4], an[MT][4];
+    u32x4 wn[TN][4], an[MT][4], nwn[NORM ? 4 : 1];
     if (c + 1 < c1) {                               // (wave-uniform: the next chunk's loads go out before this one's MFMAs)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -141,20 +199,24 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
         for (int t = 0; t < TN; ++t) wn[t][i] = load_stream(wrow[t] + (size_t)(c + 1) * 128 + 32 * i);
 #pragma unroll
         for (int m = 0; m < MT; ++m) an[m][i] = load_keep(prow[m] + (size_t)(c + 1) * 128 + 32 * i);
+        if (NORM) nwn[i] = load_keep(nrow + (size_t)(c + 1) * 128 + 32 * i);
       }
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int m = 0; m < MT; ++m)
+      for (int m = 0; m < MT; ++m) {
+        const u32x4 am = NORM ? norm_operand(a[m][i], nw[i], rstd[m]) : a[m][i];
 #pragma unroll
-        for (int t = 0; t < TN; ++t) acc[m][t] = mfma(a[m][i], w[t][i], acc[m][t]);
+        for (int t = 0; t < TN; ++t) acc[m][t] = mfma(am, w[t][i], acc[m][t]);
+      }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int t = 0; t < TN; ++t) w[t][i] = wn[t][i];
 #pragma unroll
       for (int m = 0; m < MT; ++m) a[m][i] = an[m][i];
+      if (NORM) nw[i] = nwn[i];
     }
   }
   if (wave == 3 && R > 0) {
@@ -191,6 +253,35 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
       const float sg = bf2f(f2bf(gb / (1.0f + expf(-gb))));
       jobs.C[0][(size_t)row * jobs.ldc[0] + tile * 16 + col] = f2bf(sg * ub);
     }
+  } else if (ROPE) {
+    // rope_kv_append_kernel on the sums rounded to bf16 (what it reads from the projections' output): a thread takes the
+    // pair (x[d], x[d + D / 2]) of head `hd` -- columns p and p + 8 of the tile, lanes l and l + 8 of the accumulator
+    for (int e = threadIdx.x; e < MT * TN * 128; e += 256) {
+      const int mt = e >> 7, r = (e >> 3) & 15, p = e & 7;
+      const int m = mt / TN, tt = tile * TN + mt % TN;
+      const int row = m * 16 + r, l = (r >> 2) * 16 + p, i = r & 3;
+      const int hd = tt / rope_tiles, d = (tt % rope_tiles) * 8 + p;
+      if (row >= M) continue;
+      float sa = 0.f, sb = 0.f;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) { sa += red[wv][mt][l][i]; sb += red[wv][mt][l + 8][i]; }
+      float ya = bf2f(f2bf(sa)), yb = bf2f(f2bf(sb));
+      if (job < 2) {
+        const int t = min(max(fz.pos[row], 0), fz.table_rows - 1);
+        const float *cr = fz.cs + (size_t)t * fz.D + d, *sr = fz.sn + (size_t)t * fz.D + d;
+        rope_pair(ya, yb, cr[0], cr[half], sr[0], sr[half], ya, yb);
+      }
+      u16 *dst;
+      if (job == 0) {
+        dst = jobs.C[0] + (size_t)row * jobs.ldc[0] + (size_t)hd * fz.D + d;
+      } else {
+        const int slot = fz.len[row];
+        if (slot < 0 || slot >= fz.Tmax) continue;   // a full cache: nothing is written outside it
+        dst = (job == 1 ? fz.kc : fz.vc) + (((size_t)row * fz.Tmax + slot) * fz.H + hd) * fz.D + d;
+      }
+      dst[0] = f2bf(ya);
+      dst[half] = f2bf(yb);
+    }
   } else {
     for (int e = threadIdx.x; e < MT * TN * 256; e += 256) {
       const int mt = e >> 8, l = (e >> 2) & 63, i = e & 3;
@@ -200,9 +291,25 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const 
       float s = 0.f;
 #pragma unroll
       for (int wv = 0; wv < 4; ++wv) s += red[wv][mt][l][i];
-      jobs.C[job][(size_t)row * jobs.ldc[job] + (tile * TN + t) * 16 + col] = f2bf(s);
+      const size_t n = (size_t)(tile * TN + t) * 16 + col;
+      if (RES) s = residual_add(bf2f(fz.res[(size_t)row * fz.ldres + n]), bf2f(f2bf(s)));
+      jobs.C[job][(size_t)row * jobs.ldc[job] + n] = f2bf(s);
     }
   }
+}
+
+template <int MT, int TN, bool SWIGLU>
+__global__ __launch_bounds__(256) void skinny_kernel(int M, int K, int R, const u16 *__restrict__ P, int ldp,
+                                                     const u16 *__restrict__ P2, int ldp2, SkinnyJobs jobs) {
+  skinny_body<MT, TN, SWIGLU, false, false, false>(M, K, R, P, ldp, P2, ldp2, jobs, SkinnyFused{});
+}
+
+// (R = 0: the merged planes and the head have no low-rank pair, and the r-row product of the other sources reads the
+// normed activations as a tensor)
+template <int MT, int TN, bool SWIGLU, bool NORM, bool RES, bool ROPE>
+__global__ __launch_bounds__(256) void skinny_fused_kernel(int M, int K, const u16 *__restrict__ P, int ldp, SkinnyJobs jobs,
+                                                           SkinnyFused fz) {
+  skinny_body<MT, TN, SWIGLU, NORM, RES, ROPE>(M, K, 0, P, ldp, nullptr, 0, jobs, fz);
 }
 
 // ---- rotary embedding by explicit positions ------------------------------------------------------------------
@@ -230,15 +337,8 @@ __device__ __forceinline__ void rope_rotate(const RopeCoef &r, uint4 va, uint4 v
   float a[8], b[8], ya[8], yb[8];
   unpack8(va, a);
   unpack8(vb, b);
-  {
-    // the contraction rope_vec_kernel compiles to, pinned: the second product rounded, the first fused into the sum
-#pragma clang fp contract(off)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      ya[e] = fmaf(a[e], r.c1[e], -(b[e] * r.s1[e]));
-      yb[e] = fmaf(b[e], r.c2[e], a[e] * r.s2[e]);
-    }
-  }
+  for (int e = 0; e < 8; ++e) rope_pair(a[e], b[e], r.c1[e], r.c2[e], r.s1[e], r.s2[e], ya[e], yb[e]);
   oa = pack8(ya);
   ob = pack8(yb);
 }
@@ -904,20 +1004,25 @@ extern "C" {
 // Both skinny entries: `max_m` is the entry's row limit.  M <= 32 takes the one- and two-tile kernels under the tile rule
 // they always had (the bits of msr3d_bf16_skinny_lowrank do not depend on which entry was called); 33 .. 64 rows take the
 // three- and four-tile instantiations under the wide rule below.
+// `fz` (msr3d_bf16_skinny_fused, its own checks made, at least one of nw, res, H set): the fused instantiations, under the
+// same tile rule (the bits do not depend on it).
 static int skinny_launch(int max_m, int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
-                         const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream) {
+                         const msr3d_skinny_job_t *jobs, int swiglu, msr3d_stream_t stream,
+                         const SkinnyFused *fz = nullptr) {
   if (M < 0 || M > max_m || K <= 0 || (K % 128) || R < 0 || (R % 32) || njobs < 1 || njobs > 3 || !jobs)
     return MSR3D_EINVAL;
   if (!P || ldp < K || (ldp % 8) || !al16(P)) return MSR3D_EINVAL;
   if (R > 0 && (!P2 || ldp2 < R || (ldp2 % 8) || !al16(P2))) return MSR3D_EINVAL;
   if (swiglu && (njobs != 2 || jobs[0].N != jobs[1].N || !jobs[0].C)) return MSR3D_EINVAL;
+  const bool rope = fz && fz->H > 0;
   long long rows = 0;
   bool pairs = true;                                  // every job's N a multiple of 32: two tiles a workgroup possible
   for (int j = 0; j < njobs; ++j) {
     const msr3d_skinny_job_t &jb = jobs[j];
     if (jb.N <= 0 || (jb.N % 16) || !jb.W || jb.ldw < K || (jb.ldw % 8) || !al16(jb.W)) return MSR3D_EINVAL;
     if (R > 0 && jb.B2 && (jb.ldb2 < R || (jb.ldb2 % 8) || !al16(jb.B2))) return MSR3D_EINVAL;
-    if (!(swiglu && j == 1) && (!jb.C || jb.ldc < jb.N)) return MSR3D_EINVAL;
+    // (the rotation writes k and v into the cache planes alone)
+    if (!(swiglu && j == 1) && !(rope && j > 0) && (!jb.C || jb.ldc < jb.N)) return MSR3D_EINVAL;
     rows += jb.N;
     if (jb.N % 32) pairs = false;
   }
@@ -947,20 +1052,68 @@ static int skinny_launch(int max_m, int M, int K, int R, const void *P, int ldp,
   if (swiglu) grid = sj.tiles[0];
   hipStream_t st = (hipStream_t)stream;
   const u16 *p = (const u16 *)P, *p2 = (const u16 *)P2;
-#define MSR3D_SK(MT, TN, SW) skinny_kernel<MT, TN, SW><<<(unsigned)grid, 256, 0, st>>>(M, K, R, p, ldp, p2, ldp2, sj)
-#define MSR3D_SK_MT(TN, SW)                                                                                            \
+// (the template arguments behind MT: TN, SWIGLU and, for the fused kernel, NORM, RES, ROPE)
+#define MSR3D_SK(MT, ...) skinny_kernel<MT, __VA_ARGS__><<<(unsigned)grid, 256, 0, st>>>(M, K, R, p, ldp, p2, ldp2, sj)
+#define MSR3D_SKF(MT, ...) skinny_fused_kernel<MT, __VA_ARGS__><<<(unsigned)grid, 256, 0, st>>>(M, K, p, ldp, sj, *fz)
+#define MSR3D_SK_MT(LAUNCH, ...)                                                                                       \
   switch (mt) {                                                                                                        \
-    case 1: MSR3D_SK(1, TN, SW); break;                                                                                \
-    case 2: MSR3D_SK(2, TN, SW); break;                                                                                \
-    case 3: MSR3D_SK(3, TN, SW); break;                                                                                \
-    default: MSR3D_SK(4, TN, SW); break;                                                                               \
+    case 1: LAUNCH(1, __VA_ARGS__); break;                                                                             \
+    case 2: LAUNCH(2, __VA_ARGS__); break;                                                                             \
+    case 3: LAUNCH(3, __VA_ARGS__); break;                                                                             \
+    default: LAUNCH(4, __VA_ARGS__); break;                                                                            \
   }
-  if (swiglu) { MSR3D_SK_MT(2, true) }
-  else if (tn == 2) { MSR3D_SK_MT(2, false) }
-  else { MSR3D_SK_MT(1, false) }
+  if (fz) {
+    const bool norm = fz->nw != nullptr, res = fz->res != nullptr;
+    if (swiglu) { MSR3D_SK_MT(MSR3D_SKF, 2, true, true, false, false) }
+    else if (rope && tn == 2 && norm) { MSR3D_SK_MT(MSR3D_SKF, 2, false, true, false, true) }
+    else if (rope && tn == 2) { MSR3D_SK_MT(MSR3D_SKF, 2, false, false, false, true) }
+    else if (rope && norm) { MSR3D_SK_MT(MSR3D_SKF, 1, false, true, false, true) }
+    else if (rope) { MSR3D_SK_MT(MSR3D_SKF, 1, false, false, false, true) }
+    else if (tn == 2 && norm && res) { MSR3D_SK_MT(MSR3D_SKF, 2, false, true, true, false) }
+    else if (tn == 2 && norm) { MSR3D_SK_MT(MSR3D_SKF, 2, false, true, false, false) }
+    else if (tn == 2) { MSR3D_SK_MT(MSR3D_SKF, 2, false, false, true, false) }
+    else if (norm && res) { MSR3D_SK_MT(MSR3D_SKF, 1, false, true, true, false) }
+    else if (norm) { MSR3D_SK_MT(MSR3D_SKF, 1, false, true, false, false) }
+    else { MSR3D_SK_MT(MSR3D_SKF, 1, false, false, true, false) }
+  }
+  else if (swiglu) { MSR3D_SK_MT(MSR3D_SK, 2, true) }
+  else if (tn == 2) { MSR3D_SK_MT(MSR3D_SK, 2, false) }
+  else { MSR3D_SK_MT(MSR3D_SK, 1, false) }
 #undef MSR3D_SK_MT
+#undef MSR3D_SKF
 #undef MSR3D_SK
   return (int)hipGetLastError();
+}
+
+int msr3d_bf16_skinny_fused(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,
+                            const msr3d_skinny_job_t *jobs, int swiglu, const void *norm_w, float eps, const void *res,
+                            int ldres, int H, int D, const int *pos, const int *len, const float *cos_td,
+                            const float *sin_td, int table_rows, void *k_plane, void *v_plane, int Tmax,
+                            msr3d_stream_t stream) {
+  if (R != 0 || H < 0 || njobs < 1 || njobs > 3 || !jobs) return MSR3D_EINVAL;
+  SkinnyFused fz{};
+  if (norm_w) {
+    if ((K % 512) || K > 8192 || K <= 0 || !al16(norm_w)) return MSR3D_EINVAL;     // the norm's own domain
+    fz.nw = (const u16 *)norm_w; fz.eps = eps; fz.inv_k = 1.0f / (float)K;
+  }
+  if (res) {
+    // one job, and a fresh output: the operand is read element by element while other workgroups store
+    if (njobs != 1 || swiglu || H > 0 || ldres < jobs[0].N || !al16(res) || res == jobs[0].C) return MSR3D_EINVAL;
+    fz.res = (const u16 *)res; fz.ldres = ldres;
+  }
+  if (H > 0) {
+    if (D <= 0 || (D % 32) || njobs != 3 || swiglu || Tmax <= 0 || table_rows <= 0) return MSR3D_EINVAL;
+    for (int j = 0; j < 3; ++j)
+      if (jobs[j].N != (long long)H * D) return MSR3D_EINVAL;
+    if (!pos || !len || !cos_td || !sin_td || !k_plane || !v_plane) return MSR3D_EINVAL;
+    if (!al16(cos_td) || !al16(sin_td) || !al16(k_plane) || !al16(v_plane)) return MSR3D_EINVAL;
+    fz.H = H; fz.D = D; fz.table_rows = table_rows; fz.Tmax = Tmax; fz.pos = pos; fz.len = len; fz.cs = cos_td;
+    fz.sn = sin_td; fz.kc = (u16 *)k_plane; fz.vc = (u16 *)v_plane;
+  }
+  // SwiGLU without the prologue, or nothing set: the plain entry's launch
+  const bool fused = H > 0 || res || norm_w;
+  return skinny_launch(MSR3D_SKINNY_WIDE_MAX_M, M, K, 0, P, ldp, nullptr, 0, njobs, jobs, swiglu, stream,
+                       fused ? &fz : nullptr);
 }
 
 int msr3d_bf16_skinny_lowrank(int M, int K, int R, const void *P, int ldp, const void *P2, int ldp2, int njobs,

@@ -15,32 +15,11 @@
 #include <cstdint>
 
 #include "../../include/msr3d_hip.h"
+#include "llm_rowmath.h"
 
 namespace {
 
-using u16 = unsigned short;
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {
-  unsigned u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (u16)(u >> 16);
-}
-__device__ __forceinline__ void unpack8(uint4 v, float (&f)[8]) {
-  const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  unsigned w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = (unsigned)f2bf(f[2 * i]) | ((unsigned)f2bf(f[2 * i + 1]) << 16);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
+using namespace msr3d::llm;          // u16, bf2f, f2bf, unpack8, pack8, wave_sum, the RMSNorm row arithmetic
 
 // ---- RMSNorm: one wave per row, D <= 8192, D % 512 == 0 (a lane holds D / 64 values as D / 512 x 8) ------
 // forward:  s = x (+ delta);  y = w * bf16( s * rsqrt(mean(s^2) + eps) )       (modeling_llama.LlamaRMSNorm)
@@ -61,21 +40,18 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(int M, const u16 *__re
       float d[8];
       unpack8(*reinterpret_cast<const uint4 *>(delta + o), d);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) s[v][e] = bf2f(f2bf(s[v][e] + d[e]));      // the residual stream is stored in bf16
+      for (int e = 0; e < 8; ++e) s[v][e] = residual_add(s[v][e], d[e]);
       if (sum_out) *reinterpret_cast<uint4 *>(sum_out + o) = pack8(s[v]);
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ss = fmaf(s[v][e], s[v][e], ss);
+    ss = rms_sumsq8(s[v], ss);
   }
-  const float rstd = rsqrtf(wave_sum(ss) * (1.0f / D) + eps);
+  const float rstd = rms_rstd(ss, 1.0f / D, eps);
   if (lane == 0 && rstd_out) rstd_out[row] = rstd;
 #pragma unroll
   for (int v = 0; v < V; ++v) {
-    float g[8], o8[8];
+    float g[8];
     unpack8(*reinterpret_cast<const uint4 *>(w + (v * 64 + lane) * 8), g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o8[e] = g[e] * bf2f(f2bf(s[v][e] * rstd));
-    *reinterpret_cast<uint4 *>(y + (size_t)row * D + (v * 64 + lane) * 8) = pack8(o8);
+    *reinterpret_cast<uint4 *>(y + (size_t)row * D + (v * 64 + lane) * 8) = rms_scale8(s[v], g, rstd);
   }
 }
 // backward (w frozen): g = dy * w;  dx = rstd * (g - xh * mean(g * xh)) (+ dres),  xh = s * rstd
@@ -227,7 +203,9 @@ extern "C" {
 
 int msr3d_rmsnorm_fwd(int M, int D, const void *x, const void *delta, const void *w, float eps, void *sum_out,
                       void *y, float *rstd, msr3d_stream_t stream) {
-  if (M < 0 || (D != 512 && D != 1024 && D != 2048 && D != 4096 && D != 5120 && D != 8192)) return MSR3D_EINVAL;
+  // (1536: three vectors a lane, the odd count the fused skinny product's prologue is tested against)
+  if (M < 0 || (D != 512 && D != 1024 && D != 1536 && D != 2048 && D != 4096 && D != 5120 && D != 8192))
+    return MSR3D_EINVAL;
   if (M == 0) return 0;
   if (!x || !w || !y || !al16(x) || !al16(w) || !al16(y) || (delta && !al16(delta)) || (sum_out && !al16(sum_out)))
     return MSR3D_EINVAL;
@@ -239,6 +217,7 @@ int msr3d_rmsnorm_fwd(int M, int D, const void *x, const void *delta, const void
   switch (D / 512) {
     case 1: MSR3D_RMS(1); break;
     case 2: MSR3D_RMS(2); break;
+    case 3: MSR3D_RMS(3); break;
     case 4: MSR3D_RMS(4); break;
     case 8: MSR3D_RMS(8); break;
     case 10: MSR3D_RMS(10); break;

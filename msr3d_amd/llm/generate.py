@@ -30,7 +30,7 @@ from .._lib import call, current_stream_ptr, ptr
 from .decoder import _AttentionFn, decoder_stack, rope_tables
 from .kv_cache import KVCache
 from .lora import LoRALinear, refresh_shadows, shadows_are_fresh
-from .products import E4m3Products, MergedModuleProducts, SeparateProducts
+from .products import FUSED_MAX_ROWS, E4m3Products, MergedModuleProducts, SeparateProducts
 from .search import (_embed_fn, counter_uniform_bits, gumbel_from_bits, prompt_groups, rank_answers,  # noqa: F401
                      search, torch_sample, torch_sample_scores, torch_select)
 
@@ -46,7 +46,7 @@ def _pad_tokens(x, keep, n):
 
 class CachedDecoder:
     """The decoding engine of a LoRALlamaStack (see the module docstring).  At most `max_rows` live rows (batch x beams)
-    per prefill; `search` splits a larger batch into groups of whole prompts.  THE statement of the four keywords
+    per prefill; `search` splits a larger batch into groups of whole prompts.  THE statement of the five keywords
     (LoRALlamaStack.generate and MSR3DFullStep.generate pass them on):
     weights = "bf16" (default): every product reads the bf16 base weights; a base="fp8" stack is refused.
     weights = "e4m3": a stack whose projections are all base="fp8" decodes on its own e4m3 images -- what its training
@@ -71,11 +71,21 @@ class CachedDecoder:
     `kv_kernels=False` the cache keeps bf16 planes on the bf16 kernels and rounds every write through the format in
     torch, and the e4m3 kernels give that engine's logits bit for bit.  Combines with every value of the other three
     keywords, with sampling and with prompt groups.  `score` refuses it (its cache is one prompt row read once per 64
-    suffix rows: nothing to gain), so `predict_answers` has no such keyword."""
+    suffix rows: nothing to gain), so `predict_answers` has no such keyword.
+    step = "split" (default): a layer of `step` is eight launches under lora="merged" -- the norm, q | k | v, the
+    rotation + cache append, the attention, o, the norm, gate | up, down; "fused": the three that move no weights ride
+    inside the products on msr3d_bf16_skinny_fused (`_fused_stack` states the walk): five launches a layer and the head,
+    six on an e4m3 cache, which keeps its append.  Every logit of every step and every byte written to the cache is
+    bit-identical to "split" on the same settings, so tokens, beam scores and draws are too.  Needs lora="merged" and
+    weights="bf16" (the other sources' r-row product reads the normed activations as a tensor); with every prompt_cache,
+    kv and loop.  Above products.FUSED_MAX_ROWS live rows the step runs its split launches (the same bits: a scheduling
+    choice, measured in profiles/generate_fused.txt).  `score` runs no decode step, so `predict_answers` has no such
+    keyword."""
 
     max_rows = 64          # MSR3D_SKINNY_WIDE_MAX_M: the widest skinny product (every other step kernel takes any N)
 
-    def __init__(self, stack, lora="separate", prompt_cache="rows", weights="bf16", kv="bf16", kv_kernels=True):
+    def __init__(self, stack, lora="separate", prompt_cache="rows", weights="bf16", kv="bf16", kv_kernels=True,
+                 step="split"):
         if lora not in ("separate", "merged"):
             raise ValueError(f"lora is 'separate' or 'merged', not {lora!r}")
         if prompt_cache not in ("rows", "shared"):
@@ -84,8 +94,10 @@ class CachedDecoder:
             raise ValueError(f"weights is 'bf16' or 'e4m3', not {weights!r}")
         if kv not in ("bf16", "e4m3"):
             raise ValueError(f"kv is 'bf16' or 'e4m3', not {kv!r}")
+        if step not in ("split", "fused"):
+            raise ValueError(f"step is 'split' or 'fused', not {step!r}")
         self.stack, self.lora, self.prompt_cache, self.weights = stack, lora, prompt_cache, weights
-        self.kv, self.kv_kernels = kv, bool(kv_kernels)
+        self.kv, self.kv_kernels, self.step_form = kv, bool(kv_kernels), step
         self.mods = [m for m in stack.modules() if isinstance(m, LoRALinear)]
         if weights == "bf16":
             if any(m.base == "fp8" for m in self.mods):
@@ -99,6 +111,9 @@ class CachedDecoder:
             if not self.mods or any(m.base != "fp8" for m in self.mods):
                 raise ValueError("CachedDecoder: weights='e4m3' needs a stack built with base='fp8' (a bf16 stack has no "
                                  "e4m3 images)")
+        if step == "fused" and (lora != "merged" or weights != "bf16"):
+            raise ValueError("CachedDecoder: step='fused' needs lora='merged' (and weights='bf16'): the r-row product of the "
+                             "separate and e4m3 sources reads the normed activations as a tensor, so the norm launch stays")
         if not stack.layers:
             raise ValueError("CachedDecoder: a stack without layers")
         l0 = stack.layers[0]
@@ -257,6 +272,10 @@ class CachedDecoder:
             c.reorder(beam_idx)
         cos, sin, rows = self._tables
         scale = 1.0 / math.sqrt(self.D)
+        if self.step_form == "fused" and x.shape[0] <= FUSED_MAX_ROWS:
+            logits = self._fused_stack(x, cos, sin, rows, scale)
+            c.advance()
+            return logits
         products = self.products.skinny
 
         def attend(layer, i, h):              # q | k | v in one launch; rotation + cache append; the decode attention
@@ -267,6 +286,34 @@ class CachedDecoder:
         logits = decoder_stack(st, x, attend, products)
         c.advance()
         return logits
+
+    def _fused_stack(self, x, cos, sin, table_rows, scale):
+        """step="fused": decoder.decoder_stack -- THE statement, which `step` walks above -- with every launch that moves no
+        weights folded into the product beside it (products.FusedSkinnyProducts; include/msr3d_hip.h,
+        msr3d_bf16_skinny_fused): per layer q | k | v under the input norm with the rotation and the cache append behind it,
+        the decode attention, o with the residual addition, gate | up under the second norm with SwiGLU, down with the
+        residual addition -- five launches where the split step has eight; then the head under the final norm.  The
+        residual stream is materialised by the products (x1 = x + o, x2 = x1 + y, each a fresh tensor: `x`, the caller's
+        embeddings at layer 0, is read only), so decoder_layer's `delta` never forms: bf16(x1 + y) is what the next
+        norm's launch would have stored.  Every logit and every byte written to the cache equals the split step's
+        (tests/test_generate_fused_gpu.py).  An e4m3 cache keeps its own append launch (the quantiser needs a whole head's
+        amax; the statement engine rounds the slot in torch): six launches a layer."""
+        st, c, H, D = self.stack, self.cache, self.H, self.D
+        p = self.products.fused
+        for i, layer in enumerate(st.layers):
+            a, m = layer.self_attn, layer.mlp
+            qkv, norm = (a["q_proj"], a["k_proj"], a["v_proj"]), (layer.input_layernorm_weight, layer.eps)
+            if self.kv == "bf16":
+                ck, cv, t_max = c.planes(i)
+                q, = p.project(x, qkv, norm=norm, rope=(H, D, c.pos, c.len, cos, sin, table_rows, ck, cv, t_max))
+                ctx = c.attend_appended(i, q, scale)
+            else:
+                q, k, v = p.project(x, qkv, norm=norm)
+                ctx = c.attend(i, q, k, v, cos, sin, table_rows, scale)
+            x1, = p.project(ctx, (a["o_proj"],), residual=x)
+            act = p.gated(x1, m["gate_proj"], m["up_proj"], (layer.post_attention_layernorm_weight, layer.eps))
+            x, = p.project(act, (m["down_proj"],), residual=x1)
+        return p.head(x, st.lm_head, (st.norm_weight, st.eps))
 
     # -- the token loop on the device ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -429,10 +476,10 @@ class CachedDecoder:
 
 @torch.no_grad()
 def generate(stack, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
-             kv="bf16", **search_kwargs):
+             kv="bf16", step="split", **search_kwargs):
     """LoRALlamaStack.generate: embed_tokens is the (V, hidden) table (or a callable ids -> embeddings); lora,
-    prompt_cache, weights, kv: as CachedDecoder states them; search_kwargs: everything `search` takes."""
-    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache, weights=weights, kv=kv),
+    prompt_cache, weights, kv, step: as CachedDecoder states them; search_kwargs: everything `search` takes."""
+    return search(CachedDecoder(stack, lora=lora, prompt_cache=prompt_cache, weights=weights, kv=kv, step=step),
                   _embed_fn(embed_tokens), inputs_embeds, attention_mask, **search_kwargs)
 
 

@@ -187,21 +187,39 @@ class KVCache:
         the codes and exponents; as the statement (kernels=False), the bf16 launches with the appended slot rounded in
         between -- gathered and scattered by the device `len`, no synchronisation."""
         N, H, D = self.rows, self.heads, self.head_dim
-        HD, ws = H * D, self.workspace
+        HD = H * D
         ck, cv = self.k(layer), self.v(layer)
-        ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=q.device)
         if self.codes:
+            ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=q.device)
             return self._attend_codes(layer, q, k, v, cos, sin, table_rows, scale, ctx)
         with torch.cuda.device(q.device):
-            s = current_stream_ptr(q.device)
             call("msr3d_rope_kv_append", N, H, D, ck.shape[1], ptr(q), ptr(k), ptr(v), HD, ptr(self.pos), ptr(self.len),
-                 ptr(cos), ptr(sin), table_rows, ptr(ck), ptr(cv), s)
+                 ptr(cos), ptr(sin), table_rows, ptr(ck), ptr(cv), current_stream_ptr(q.device))
             if self.rounds:
                 # (a full cache: nothing was appended and the last slot, rounded already, is rounded again: unchanged)
                 rows = torch.arange(N, device=q.device)
                 slot = self.len.long().clamp(0, ck.shape[1] - 1)
                 ck[rows, slot] = _kv_round(ck[rows, slot])
                 cv[rows, slot] = _kv_round(cv[rows, slot])
+        return self.attend_appended(layer, q, scale)
+
+    def planes(self, layer):
+        """-> (k plane, v plane, slots a row) of `layer` as a step appends to them: what msr3d_rope_kv_append is given
+        (shared: the tail planes).  For a product that does the append itself (step="fused", the plain bf16 cache)."""
+        ck = self.k(layer)
+        return ck, self.v(layer), ck.shape[1]
+
+    def attend_appended(self, layer, q, scale):
+        """`attend` from its second launch on, for the bf16 planes: q (rows, heads head_dim) is rotated and slot `len`
+        holds the new token's k, v already -> context."""
+        if self.codes:
+            raise RuntimeError("KVCache.attend_appended: the e4m3 cache appends through `attend` (its quantiser)")
+        N, H, D = self.rows, self.heads, self.head_dim
+        HD, ws = H * D, self.workspace
+        ck, cv = self.k(layer), self.v(layer)
+        ctx = torch.empty((N, HD), dtype=torch.bfloat16, device=q.device)
+        with torch.cuda.device(q.device):
+            s = current_stream_ptr(q.device)
             if self.shared:
                 call("msr3d_attn_decode_shared", self.prompts, N // self.prompts, self.t_prompt, self.t_tail, H, D, ptr(q),
                      HD, ptr(self.prompt_kv[layer, 0]), ptr(self.prompt_kv[layer, 1]), ptr(self.prompt_keep), ptr(ck),

@@ -134,6 +134,7 @@ class MergedModuleProducts(ModuleProducts):
     def __init__(self, planes):
         self.planes = planes
         self.skinny = SkinnyProducts(self)
+        self.fused = FusedSkinnyProducts(self)              # (step="fused": the same planes, fewer launches)
 
     def project(self, h, mods):
         x2 = _eval_rows(h, "MergedModuleProducts: merged weights are for evaluation (no backward); call under "
@@ -152,6 +153,60 @@ class MergedModuleProducts(ModuleProducts):
 
     def job(self, m, K, C):
         return _lib.SkinnyJob(self.planes[m].data_ptr(), K, 0, 0, C, m.out_features, m.out_features)
+
+
+# step="fused" runs its fused launches up to this many live rows; above, the step is the split sequence (the same bits).
+# A prologue launch normalises its activations again in every workgroup (and walks all M rows for their rstd first), which
+# grows with M while the launches it saves do not: measured (profiles/generate_fused.txt) faster than split up to 10 rows,
+# level with it at 15 and 8-12 % slower at 20, where the product takes its second activation tile.
+FUSED_MAX_ROWS = 15
+
+
+class FusedSkinnyProducts:
+    """step="fused": MergedModuleProducts.skinny with the launches around each product folded into it -- ONE call of
+    msr3d_bf16_skinny_fused per product, R = 0 (include/msr3d_hip.h states the three pieces and why each gives the bits of
+    the launch it replaces).  `norm` = (weight, eps): the product reads RMSNorm(h) weight; `residual`: the output is
+    bf16(residual + product), a fresh tensor; `rope` (q | k | v on a bf16 cache) = (H, D, pos, len, cos, sin, table_rows,
+    k_plane, v_plane, Tmax): q comes back rotated, k and v go into the planes alone."""
+
+    def __init__(self, src):
+        self.src = src
+
+    def _call(self, h, jobs, swiglu, norm=None, residual=None, rope=None):
+        M, K = h.shape
+        nw, eps = norm if norm is not None else (None, 0.0)
+        tail = (rope[0], rope[1], *(ptr(t) for t in rope[2:6]), rope[6], ptr(rope[7]), ptr(rope[8]), rope[9]) \
+            if rope is not None else (0, 0, ptr(None), ptr(None), ptr(None), ptr(None), 0, ptr(None), ptr(None), 0)
+        with torch.cuda.device(h.device):
+            call("msr3d_bf16_skinny_fused", M, K, 0, ptr(h), K, ptr(None), 0, len(jobs), jobs, int(swiglu), ptr(nw),
+                 ctypes.c_float(eps), ptr(residual), residual.shape[1] if residual is not None else 0, *tail,
+                 current_stream_ptr(h.device))
+
+    def project(self, h, mods, norm=None, residual=None, rope=None):
+        """-> one (M, N) tensor per module; under `rope` q alone."""
+        M, K = h.shape
+        outs = [torch.empty((M, m.out_features), dtype=torch.bfloat16, device=h.device)
+                for m in (mods[:1] if rope is not None else mods)]
+        jobs = (_lib.SkinnyJob * len(mods))()
+        for n, m in enumerate(mods):
+            jobs[n] = self.src.job(m, K, outs[n].data_ptr() if n < len(outs) else 0)
+        self._call(h, jobs, False, norm, residual, rope)
+        return outs
+
+    def gated(self, h, gate, up, norm):
+        M, K = h.shape
+        act = torch.empty((M, gate.out_features), dtype=torch.bfloat16, device=h.device)
+        jobs = (_lib.SkinnyJob * 2)(self.src.job(gate, K, act.data_ptr()), self.src.job(up, K, 0))
+        self._call(h, jobs, True, norm)
+        return act
+
+    def head(self, h, lm_head, norm):
+        lm_head._sync()
+        M, K, V = h.shape[0], lm_head.in_features, lm_head.out_features
+        logits = torch.empty((M, V), dtype=torch.bfloat16, device=h.device)
+        self._call(h, (_lib.SkinnyJob * 1)(_lib.SkinnyJob(lm_head.weight.data_ptr(), K, 0, 0, logits.data_ptr(), V, V)),
+                   False, norm)
+        return logits
 
 
 class E4m3Products(ModuleProducts):

@@ -165,7 +165,7 @@ class LoRALlamaStack(nn.Module):
                                  slice(from_position, None) if from_position > 0 else None)
 
     def generate(self, inputs_embeds, attention_mask, embed_tokens, lora="separate", prompt_cache="rows", weights="bf16",
-                 kv="bf16", **search_kwargs):
+                 kv="bf16", step="split", **search_kwargs):
         """Greedy / beam search or sampling from prompt embeddings over a key / value cache (msr3d_amd/llm/generate.py)
         -> (B x num_return_sequences, <= max_length) int64 generated tokens, a prompt's rows adjacent.  embed_tokens: the
         (V, hidden) embedding table (or a callable ids -> embeddings); search_kwargs: bos_id, eos_id, pad_id, num_beams,
@@ -191,10 +191,15 @@ class LoRALlamaStack(nn.Module):
         loop = "host" (default): one host decision and synchronisation per token; loop = "device" (greedy and beam
         search, not sampling): a token is a replay of a captured graph, the beam bookkeeping two kernels
         (msr3d_beam_advance / msr3d_greedy_advance), and the host reads `done` every `poll` (default 4) tokens --
-        `search` and CachedDecoder.token_loop state it; ties go to the lower index, where the host loop leaves them open."""
+        `search` and CachedDecoder.token_loop state it; ties go to the lower index, where the host loop leaves them open.
+        step = "split" (default): a layer of the decode step is its products and, between them, two norms and the
+        rotation + cache append as launches of their own; step = "fused" (lora="merged" only): those ride inside the
+        products (msr3d_bf16_skinny_fused) -- five launches a layer for eight, six on an e4m3 cache, up to
+        products.FUSED_MAX_ROWS live rows (above: the split step) -- every logit and cache byte the same bits, so the same
+        tokens (CachedDecoder states it; profiles/generate_fused.txt has what it measured)."""
         from .generate import generate
         return generate(self, inputs_embeds, attention_mask, embed_tokens, lora=lora, prompt_cache=prompt_cache,
-                        weights=weights, kv=kv, **search_kwargs)
+                        weights=weights, kv=kv, step=step, **search_kwargs)
 
     def predict_answers(self, inputs_embeds, attention_mask, embed_tokens, answer_ids, answer_mask, lora="separate",
                         weights="bf16", **rank_kwargs):

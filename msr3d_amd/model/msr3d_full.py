@@ -140,7 +140,7 @@ class MSR3DFullStep(MSR3DHotPath):
     def generate(self, data_dict, num_beams=5, max_length=256, min_length=1, repetition_penalty=3.0, length_penalty=1.0,
                  max_out_len=256, bos_id=1, eos_id=2, use_nucleus_sampling=False, top_p=0.9, temperature=1.0,
                  num_captions=1, seed=None, top_k=50, lora="separate", prompt_cache="rows", weights="bf16",
-                 loop="host", poll=4, kv="bf16"):
+                 loop="host", poll=4, kv="bf16", step="split"):
         """The reference's MSR3D.generate: hot path -> prompt embeddings with the scene tokens written in and the object
         mask at their positions (prompt only, no answer) -> one bos embedding and a mask column of ones appended -> beam
         search (or sampling) over the key / value cache (`max_length` counts generated tokens) -> id 0 mapped to 2 ->
@@ -164,7 +164,9 @@ class MSR3DFullStep(MSR3DHotPath):
         (LoRALlamaStack.generate; not with use_nucleus_sampling).
         kv = "e4m3": the key / value cache as e4m3 codes with a power-of-two scale per (slot, head): half the cache and
         half the attention's and the beam reorder's bytes; logits about 3 % rel-L2 from the default "bf16", so captions
-        may differ (LoRALlamaStack.generate)."""
+        may differ (LoRALlamaStack.generate).
+        step = "fused" (with lora="merged"): the decode step's norms, rotation and cache append inside its products, five
+        launches a layer for eight -- the same tokens as the default "split" (LoRALlamaStack.generate)."""
         if not data_dict["input_ids"].is_cuda:
             raise RuntimeError("MSR3DFullStep runs on the GPU only (the language-model kernels have no CPU fallback)")
         if max_length > max_out_len:
@@ -188,7 +190,8 @@ class MSR3DFullStep(MSR3DHotPath):
                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                       do_sample=bool(use_nucleus_sampling), top_p=top_p, top_k=top_k,
                                       temperature=temperature, num_return_sequences=num_captions, seed=seed, lora=lora,
-                                      prompt_cache=prompt_cache, weights=weights, loop=loop, poll=poll, kv=kv)
+                                      prompt_cache=prompt_cache, weights=weights, loop=loop, poll=poll, kv=kv,
+                                      step=step)
         out = torch.where(out == 0, torch.full_like(out, 2), out)
         pad = torch.full((out.shape[0], max_out_len - out.shape[1]), 2, dtype=out.dtype, device=out.device)
         d["output_tokens"] = torch.cat([out, pad], 1)

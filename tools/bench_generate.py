@@ -22,6 +22,9 @@ Device events around every repeat (warm-up first, >= 20 repeats): median and spr
                                                  #   search(loop="host") and loop="device" (graph replays), alternating;
                                                  #   the capture's cost per group; the `poll` sweep; --layers-once 32 adds
                                                  #   one cell on a 32-layer stack
+    python tools/bench_generate.py --step both --lora merged [--loop host|device|both]   # whole tokens under step="split"
+                                                 #   and step="fused", alternating call by call; the fused products' launches
+                                                 #   beside the split launches they replace; --layers-once 32 as above
 """
 import argparse
 import json
@@ -506,6 +509,126 @@ def loop_cells(args):
     print(json.dumps(out))
 
 
+def step_launches(net, rows, length, gen, emb, steps=5):
+    """Per-launch device time (the binding's census: events around EVERY library launch) of a split and of a fused step at
+    `rows` x `length`, medians over layers and `steps` steps: the fused products by their place in the layer, and of the
+    split step the same products, the norm in front of q | k | v and of gate | up, the final norm, and the append."""
+    from msr3d_amd.llm.products import skinny_entry
+    x = (torch.randn(1, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+    mask = torch.ones(1, length, dtype=torch.int64, device="cuda")
+    tok = emb[torch.randint(0, VOCAB, (rows,), generator=gen, device="cuda")]
+    layers = len(net.layers)
+    out = {}
+    for form in ("split", "fused"):
+        eng = CachedDecoder(net, lora="merged", step=form)
+        eng.reserve(rows, steps + 8)
+        eng.prefill(x, mask)
+        eng.expand(rows)
+        for _ in range(3):
+            eng.step(tok)
+        sink = {}
+        _lib.set_timing_sink(sink, census=True)
+        try:
+            for _ in range(steps):
+                eng.step(tok)
+            torch.cuda.synchronize()
+        finally:
+            _lib.set_timing_sink(None)
+        us = {k: [e0.elapsed_time(e1) * 1e3 for e0, e1 in v] for k, v in sink.items()}
+        med = lambda t: round(statistics.median(t), 1)                       # noqa: E731
+
+        def by_place(ts, per_layer, names):
+            """a launch list in step order, `per_layer` a layer and one more at the step's end -> medians by place."""
+            per_step = per_layer * layers + 1
+            assert len(ts) == per_step * steps, (len(ts), per_step, steps)
+            cols = [[] for _ in names]
+            for i, t in enumerate(ts):
+                j = i % per_step
+                cols[per_layer if j == per_step - 1 else j % per_layer].append(t)
+            return {n: med(c) for n, c in zip(names, cols)}
+        if form == "fused" and "msr3d_bf16_skinny_fused" in us:
+            out[form] = by_place(us["msr3d_bf16_skinny_fused"], 4, ("q|k|v", "o", "gate|up", "down", "head"))
+        else:
+            out[form] = {**by_place(us[skinny_entry(rows)], 4, ("q|k|v", "o", "gate|up", "down", "head")),
+                         **{"norm_" + k: v for k, v in by_place(us["msr3d_rmsnorm_fwd"], 2, ("in", "post", "final")).items()},
+                         "append": med(us["msr3d_rope_kv_append"])}
+        out[form]["attention"] = med(us["msr3d_attn_decode"])
+        del eng
+    return out
+
+
+def step_cells(args):
+    """--step: whole tokens of `search` on merged weights under step="split" (the parent's step) and step="fused",
+    alternating call by call in one process, under --loop host (default), device or both -- loop_cells' clock: host time
+    around whole `search` calls that end in a synchronise, a token = (T(SHORT + RUN tokens) - T(SHORT tokens)) / RUN.
+    Rows are whole prompts of 5 beams (1 row: greedy).  Beside every cell the streaming floor; per row count the
+    per-launch times of the fused products and of the split launches they replace (step_launches)."""
+    from msr3d_amd.llm.generate import _embed_fn, search
+    from msr3d_amd.llm.products import FUSED_MAX_ROWS
+    SHORT, RUN = 8, 32
+    forms = ["split", "fused"] if args.step == "both" else [args.step]
+    loops = ["host", "device"] if args.loop == "both" else [args.loop or "host"]
+    emb = torch.randn(VOCAB, HIDDEN, device="cuda").to(torch.bfloat16) * 0.02
+    embed = _embed_fn(emb)
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def call(net, x, mask, beams, loop, form, tokens):
+        kw = dict(loop="device", poll=args.poll) if loop == "device" else {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = search(CachedDecoder(net, lora="merged", step=form), embed, x, mask, eos_id=None, num_beams=beams,
+                     max_length=tokens, min_length=1, repetition_penalty=3.0, **kw)
+        out.cpu()
+        return time.perf_counter() - t0
+
+    def cell(net, layers, rows, length):
+        beams = 1 if rows < BEAMS else BEAMS
+        prompts = max(1, rows // beams)
+        x = (torch.randn(prompts, length, HIDDEN, generator=gen, device="cuda") * 0.5).to(torch.bfloat16)
+        mask = torch.ones(prompts, length, dtype=torch.int64, device="cuda")
+        variants = [(lp, f) for lp in loops for f in forms]
+        ts = {v: ([], []) for v in variants}
+        for r in range(args.repeats + 1):                         # (the first repeat is the warm-up)
+            for v in variants:
+                a, b = call(net, x, mask, beams, *v, SHORT), call(net, x, mask, beams, *v, SHORT + RUN)
+                if r:
+                    ts[v][0].append(a)
+                    ts[v][1].append(b)
+        c = {"layers": layers, "live_rows": prompts * beams, "prompts": prompts, "beams": beams, "length": length,
+             "runs_fused_launches": prompts * beams <= FUSED_MAX_ROWS,
+             "floor_us": round(step_bytes(layers, prompts * beams, length + SHORT + RUN // 2) / COPY_RATE * 1e6, 1)}
+        for lp in loops:
+            c[lp] = {f: _stats(sorted((b - a) / RUN * 1e6 for a, b in zip(*ts[(lp, f)]))) for f in forms}
+            if len(forms) == 2:
+                sp, fu = c[lp]["split"], c[lp]["fused"]
+                c[lp]["fused_over_split"] = round(fu["median_us"] / sp["median_us"], 3)
+                # by spread: slower when fused's minimum lies above split's maximum, faster the other way round
+                c[lp]["verdict"] = ("slower" if fu["min_us"] > sp["max_us"] else
+                                    "faster" if fu["max_us"] < sp["min_us"] else "within the spread")
+        return c
+
+    out = {"bench": "generate_step", "device": torch.cuda.get_device_name(0), "hidden": HIDDEN, "heads": HEADS, "vocab": VOCAB,
+           "repeats": args.repeats, "tokens_timed": RUN, "poll": args.poll, "loops": loops, "forms": forms,
+           "fused_max_rows": FUSED_MAX_ROWS, "cells": [], "launches_us": {}}
+    if args.layers:
+        net = build(args.layers)
+        net.merged_weights()
+        for rows in (int(r) for r in (args.rows or "1,5,20,60").split(",")):
+            for length in (int(t) for t in args.lengths.split(",")):
+                out["cells"].append(cell(net, args.layers, rows, length))
+                print(json.dumps(out["cells"][-1]), file=sys.stderr, flush=True)
+            if len(forms) == 2:
+                out["launches_us"][str(rows)] = step_launches(net, rows, 320, gen, emb)
+                print(json.dumps({"launches_us": {rows: out["launches_us"][str(rows)]}}), file=sys.stderr, flush=True)
+        del net
+    if args.layers_once:
+        torch.cuda.empty_cache()
+        net = build(args.layers_once)
+        net.merged_weights()
+        out["cells"].append(cell(net, args.layers_once, 20, 320))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sample", action="store_true", help="time the draw kernel beside the select kernel and a step")
@@ -525,11 +648,18 @@ def main():
                          "both: the two caches in turn, and the attention, append and reorder launches of each")
     ap.add_argument("--loop", default="", choices=("", "host", "device", "both"),
                     help="time whole tokens of search under that token loop; both: the two loops in turn")
+    ap.add_argument("--step", default="", choices=("", "split", "fused", "both"),
+                    help="time whole tokens of search on merged weights (--lora merged) under that step form, with --loop "
+                         "host|device|both; both: the two forms in turn, and the fused products' launches beside the split ones")
     ap.add_argument("--poll", type=int, default=4, help="--loop: tokens between two reads of `done`")
     ap.add_argument("--polls", default="1,4,8,16", help="--loop: the values of poll swept at three cells")
     ap.add_argument("--layers-once", type=int, default=0, help="--loop: one more cell (20 x 320) on a stack this deep")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_generate needs a GPU"
+    if args.step:
+        if args.lora != "merged":
+            ap.error("--step needs --lora merged (step='fused' runs on the merged planes)")
+        return step_cells(args)
     if args.loop:
         return loop_cells(args)
     if args.sample:
