@@ -12,7 +12,7 @@
 //                                                in slab order, by the next msr3d_scene_rows launch
 //
 // with the middle = spatial attention of one head (attn_core.h), GELU + dropout, or their backward.
-// One workgroup per (scene, slice) -- the attention forward: two, one per half of the query rows -- of
+// One workgroup per (scene, slice) -- the attention blocks: two, one per half of the token rows -- of
 // eight waves; four for the linear blocks.  The (tokens x 2048) activation, q / k / v and the context vectors never go
 // through HBM between the two products (they are written once, as side outputs for the backward).
 //
@@ -36,6 +36,8 @@
 // fast boxes and 14 us a step slower on the others: off.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "../../include/msr3d_hip.h"
 #include "attn_core.h"
 #include "rowmath.h"
@@ -51,6 +53,10 @@
 #endif
 #ifndef MSR3D_FFN_SCENE_XCD
 #define MSR3D_FFN_SCENE_XCD 0
+#endif
+// the attention backward's form when the environment does not say (MSR3D_ATTN_BWD_SPLIT): scene_attn_bwd3_kernel
+#ifndef MSR3D_ATTN_BWD_SPLIT_DEFAULT
+#define MSR3D_ATTN_BWD_SPLIT_DEFAULT 1
 #endif
 
 namespace {
@@ -151,15 +157,16 @@ __device__ __forceinline__ void stage_f32(const float *__restrict__ a0, int lda,
 
 // product-2 epilogue: this slice's partial product -> its slab.  D = W X^T: lane (j, g) holds channels
 // n0 + 16 rn + 4 g .. + 3 of token 16 mt + j -- one 16-byte store per tile, 64 contiguous bytes per row
-template <int RN>
-__device__ __forceinline__ void store_partials(const f32x4 (&acc)[RN][4], float *__restrict__ slab, int row_base,
-                                               int L, int n0, int lane) {
+// (MT row tiles from row r0 of the scene on)
+template <int RN, int MT = 4>
+__device__ __forceinline__ void store_partials(const f32x4 (&acc)[RN][MT], float *__restrict__ slab, int row_base,
+                                               int L, int n0, int lane, int r0 = 0) {
   const int j = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int rn = 0; rn < RN; ++rn)
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int row = 16 * mt + j;
+    for (int mt = 0; mt < MT; ++mt) {
+      const int row = r0 + 16 * mt + j;
       if (row < L)
         st4(slab + (size_t)(row_base + row) * KD + n0 + 16 * rn + 4 * g,
             make_float4(acc[rn][mt][0], acc[rn][mt][1], acc[rn][mt][2], acc[rn][mt][3]));
@@ -621,24 +628,72 @@ __global__ __launch_bounds__(512) void scene_attn_fwd2_kernel(const SB p) {
 // an 8-piece product), all eight weight pieces of product 1 sit in registers before the product starts, and the core's
 // dq / dk / dv come out transposed per tile (attn_core.h: strip_mma's SWAP) so that the side outputs are 16-byte stores
 // and product 2's operand 8-byte LDS stores.
+//
+// NWG = 2 (MSR3D_ATTN_BWD_SPLIT, read by msr3d_scene_block at every call): TWO workgroups per (scene, head), 256 at the
+// bench shape.  Workgroup (h, rh) owns the token rows [32 rh, 32 rh + 32) twice over -- as QUERIES it produces their dq and
+// cond gradients, as KEYS their dk and dv -- so every row of dqkvc and of the head's partial slab is complete in, and
+// stored by, one workgroup; the two never talk to each other.  Each computes for itself what both need (d ctx and dP of
+// all 64 rows, every query's row dots), d logit on three quadrants (own queries x all keys, other queries x own keys),
+// the sigmoid / pairwise part -- and with it the pairwise slab -- for its own queries only, and product 2 over its own
+// two row tiles.  The SAME BITS as NWG = 1: a (16-row tile, 16-column half) unit of dq / dk / dv is still one strip_mma
+// chain over all 64 keys / queries -- 12 units dealt whole to the eight waves: dq to waves 0 .. 3, dk and dv to waves
+// 4 .. 7 (a SIMD's two waves, w and w + 4, hold three) -- and a (row, key half)'s row dot and cond partials are still two
+// terms a lane and a row16_sum, met as half 0 + half 1.  The sigmoid part is dealt again, (row pair, key half) to a wave:
+// 4 pairs a lane instead of 8, on d logit read back from LDS.  The planes arrive own half first (scene_attn_fwd2_kernel).
 // =====================================================================================================
 constexpr int kAttnBwd3Aux = kAttnBwdAux + 2 * 64 * 4 + 2 * 64 * 8 * 4;     // + row dots [2][64] + cond partials [2][64][8]
 constexpr int kAttnBwd3Lds = XS_BYTES + kAttnBwd3Aux;
 
+// One query row's share of the sigmoid / pairwise backward over a key half: the lane's two pairs (keys col0, col0 + 16),
+// then the 16 lanes of the row group -> the partial (d bias, d w[5]) of (row, key half) at `o` (lane i == 0).
+// `pl0`: the row's pairwise features, [key][SD].
+__device__ __forceinline__ void cond_grad_row(const msr3d_attn::RowCond &c, const float *pl0, bool rowok, int col0,
+                                              const float (&dl)[2], const bool (&keyok)[2], float *o, bool lead) {
+  float gb = 0.f, gw[SD];
+#pragma unroll
+  for (int d = 0; d < SD; ++d) gw[d] = 0.f;
+#pragma unroll
+  for (int rn = 0; rn < 2; ++rn) {
+    if (rowok && keyok[rn]) {
+      const float *pl = pl0 + (size_t)(col0 + 16 * rn) * SD;
+      float z = c.bias;
+#pragma unroll
+      for (int d = 0; d < SD; ++d) z = fmaf(c.w[d], pl[d], z);
+      const float loc = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+      const float dz = (loc >= 1e-6f) ? dl[rn] * (1.0f - loc) : 0.f;   // (attn_core.h: d log(max(loc, 1e-6)) / dz)
+      gb += dz;
+#pragma unroll
+      for (int d = 0; d < SD; ++d) gw[d] = fmaf(dz, pl[d], gw[d]);
+    }
+  }
+  gb = msr3d_attn::row16_sum(gb);
+#pragma unroll
+  for (int d = 0; d < SD; ++d) gw[d] = msr3d_attn::row16_sum(gw[d]);
+  if (lead) {
+    o[0] = gb;
+#pragma unroll
+    for (int d = 0; d < SD; ++d) o[1 + d] = gw[d];
+  }
+}
+
+template <int NWG>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void scene_attn_bwd3_kernel(const SB p) {
+  constexpr bool SPLIT = NWG == 2;
+  static_assert(NWG == 1 || NWG == 2, "one workgroup per (scene, head), or one per half of its rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned short *xs = reinterpret_cast<unsigned short *>(smem);
   unsigned char *aux = smem + XS_BYTES;
+  int h = blockIdx.x & 7, rh = blockIdx.x >> 3, b = blockIdx.y;
 #if MSR3D_ATTN_SCENE_XCD
-  int h, b;
-  if ((gridDim.y & 7) == 0) {
-    const int id = blockIdx.y * 8 + blockIdx.x, c = id & 7, jj = id >> 3;
-    b = c + 8 * (jj >> 3); h = jj & 7;
-  } else { h = blockIdx.x; b = blockIdx.y; }
-  const int L = p.L, H = p.H, ldq = p.ldq;
-#else
-  const int h = blockIdx.x, b = blockIdx.y, L = p.L, H = p.H, ldq = p.ldq;
+  if ((gridDim.y & 7) == 0) {                // a scene's 8 NWG workgroups on ONE XCD (workgroup id mod 8)
+    const int id = blockIdx.y * (8 * NWG) + blockIdx.x, c = id & 7, jj = id >> 3, x = jj & (8 * NWG - 1);
+    b = c + 8 * (jj / (8 * NWG)); h = x & 7; rh = x >> 3;
+  }
 #endif
+  const int L = p.L, H = p.H, ldq = p.ldq;
+  const int q0 = SPLIT ? 32 * rh : 0;        // the rows this workgroup owns: [q0, q0 + NQ)
+  constexpr int NQ = TM / NWG;
+  if (SPLIT && q0 >= L) return;              // (a scene of <= 32 tokens: the first workgroup owns every row)
   const int row_base = b * L;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -655,11 +710,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
   for (int q = 0; q < 4; ++q) load_wpiece(ring1[q], w1, q, 0);
   // the scene's planes, the head's saved q / k / v (one float4 a thread and tile), cond, probabilities
-  uint4 xv[12];
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(p.xp + (size_t)b * 3 * TM * KD);
+  // (two workgroups: the own 32 rows now, the other half's when those have arrived -- scene_attn_fwd2_kernel)
+  uint4 xv[4 * kPlanes], xw[2 * kPlanes];
+  const uint4 *xsrc = reinterpret_cast<const uint4 *>(p.xp + (size_t)b * 3 * TM * KD);
+  if (!SPLIT) {
 #pragma unroll
-    for (int k = 0; k < 4 * kPlanes; ++k) xv[k] = src[tid + 512 * k];
+    for (int k = 0; k < 4 * kPlanes; ++k) xv[k] = xsrc[tid + 512 * k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 2 * kPlanes; ++k) {
+      const int q = tid + 512 * k, plane = q >> 10, row = q0 + ((q >> 5) & 31), c8 = q & 31;
+      xv[k] = xsrc[plane * 2048 + row * 32 + c8];
+    }
   }
   float4 tq[3];
   {
@@ -673,28 +735,53 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int row = tid >> 3, c = tid & 7;
     tc = (row < L && c < SD + 1) ? p.qkvc[(size_t)(row_base + row) * ldq + 3 * KD + h * (SD + 1) + c] : 0.f;
   }
-  const float *plsrc = p.ploc + (size_t)b * L * L * SD, *prsrc = p.probs + ((size_t)b * H + h) * L * L;
-  const int pn = L * L * SD, qn = L * L;
+  // the pairwise rows of the own queries (two workgroups: that half of the slab), all of the head's probabilities
+  const float *plsrc = p.ploc + ((size_t)b * L + q0) * L * SD, *prsrc = p.probs + ((size_t)b * H + h) * L * L;
+  const int pn = min(NQ, L - q0) * L * SD, qn = L * L;
   // both slabs as 16-byte vectors whatever their alignment (L = 61: the agent token of 'as_object'): Slab4
   const Slab4 pls = make_slab4(plsrc, pn), prs = make_slab4(prsrc, qn);
   const bool qrow4 = prs.mis == 0 && (L & 3) == 0;      // a vector of probabilities never straddles a row
-  float4 prv[2], plv[10];
+  constexpr int NPL = NQ * TM * SD / 4 / 512;           // 10 (5) float4 a thread
+  float4 prv[2], plv[NPL];
   // (the slab is asked for WITH the planes: behind them and ahead of product 1's last pieces it was waited for with those
   //  pieces -- loads complete in order)
 #pragma unroll
-  for (int k = 0; k < 10; ++k) plv[k] = slab4_load(pls, tid + 512 * k);
+  for (int k = 0; k < NPL; ++k) plv[k] = slab4_load(pls, tid + 512 * k);
 #pragma unroll
   for (int k = 0; k < 2; ++k) prv[k] = slab4_load(prs, tid + 512 * k);
+  if (SPLIT) {
+    // the own half into LDS as soon as IT is here (what was asked for behind it stays in flight), then the other half: the
+    // pair's two workgroups miss on disjoint halves and find, in their XCD's L2, what the partner has fetched
+#pragma unroll
+    for (int k = 0; k < 2 * kPlanes; ++k) {
+      const int q = tid + 512 * k, plane = q >> 10, row = q0 + ((q >> 5) & 31), c8 = q & 31;
+      *reinterpret_cast<uint4 *>(xs + plane * PLANE + row * PITCH + c8 * 8) = xv[k];
+    }
+    __builtin_amdgcn_sched_barrier(0);     // (the other half's loads stay behind the own half's stores)
+#pragma unroll
+    for (int k = 0; k < 2 * kPlanes; ++k) {
+      const int q = tid + 512 * k, plane = q >> 10, row = (32 - q0) + ((q >> 5) & 31), c8 = q & 31;
+      xw[k] = xsrc[plane * 2048 + row * 32 + c8];
+    }
+  }
   {
     const int row = tid >> 3, c4 = (tid & 7) * 4;
 #pragma unroll
     for (int t = 0; t < 3; ++t) st4(sq + t * TM * LD32 + row * LD32 + c4, tq[t]);
     scond[tid] = tc;
+    if (!SPLIT) {
 #pragma unroll
-    for (int k = 0; k < 4 * kPlanes; ++k) {
-      const int q = tid + 512 * k;
-      const int plane = q >> 11, row2 = (q >> 5) & 63, c8 = q & 31;
-      *reinterpret_cast<uint4 *>(xs + plane * PLANE + row2 * PITCH + c8 * 8) = xv[k];
+      for (int k = 0; k < 4 * kPlanes; ++k) {
+        const int q = tid + 512 * k;
+        const int plane = q >> 11, row2 = (q >> 5) & 63, c8 = q & 31;
+        *reinterpret_cast<uint4 *>(xs + plane * PLANE + row2 * PITCH + c8 * 8) = xv[k];
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2 * kPlanes; ++k) {
+        const int q = tid + 512 * k, plane = q >> 10, row2 = (32 - q0) + ((q >> 5) & 31), c8 = q & 31;
+        *reinterpret_cast<uint4 *>(xs + plane * PLANE + row2 * PITCH + c8 * 8) = xw[k];
+      }
     }
   }
   // (the planes' registers are free) the rest of product 1's pieces
@@ -752,21 +839,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (row >= L || col >= L) sp[row * LDP + col] = 0.f;
   }
 #pragma unroll
-  for (int k = 0; k < 10; ++k) {
+  for (int k = 0; k < NPL; ++k) {
     const int e = tid + 512 * k;
     if (e < pls.n4) reinterpret_cast<float4 *>(spl)[e] = plv[k];
   }
-  const float *plb = spl + pls.mis;
+  const float *plb = spl + pls.mis;        // (element 0: row q0, key 0)
   __syncthreads();
   SB_STAMP(5);
-  // ---- the core: wave (t, kh) ----
+  // ---- the core: wave (t, kh) for dP and the row dots; one workgroup: for everything ----
   const int t = wave & 3, kh = wave >> 2, row0 = 16 * t, i = j;
+  // the wave's (tile, column half) unit of dq / dk / dv -- two workgroups: dq (waves 0 .. 3) or dk and dv (4 .. 7)
+  const int ut = SPLIT ? 2 * rh + (wave & 1) : t, uc = SPLIT ? (wave >> 1) & 1 : kh, urow0 = 16 * ut;
+  const bool has_q = !SPLIT || wave < 4, has_kv = !SPLIT || wave >= 4;
   f32x4 oq[1], ok[1], ov[1];
   {
     f32x4 dP[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     msr3d_attn::strip_mma<kCoreMma, 2, DH, true, true>(sdo, LD32, sv + 32 * kh * LD32, LD32, row0, dP, lane);
     ov[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    msr3d_attn::strip_mma<kCoreMma, 1, TM, false, false, true>(sp, LDP, sdo + 16 * kh, LD32, row0, ov, lane);
+    if (has_kv) msr3d_attn::strip_mma<kCoreMma, 1, TM, false, false, true>(sp, LDP, sdo + 16 * uc, LD32, urow0, ov, lane);
     __syncthreads();                       // every wave is done reading P as a matrix operand
     const unsigned char *pad_b = p.pad + (size_t)b * L;
     bool keyok[2];
@@ -793,66 +883,68 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int r = 0; r < 4; ++r) {
       const int row = row0 + 4 * g + r;
       const float dot = xdot[row] + xdot[64 + row];
-      const msr3d_attn::RowCond c = msr3d_attn::load_cond(scond, 8, L, row);
-      float gb = 0.f, gw[SD];
+      float dl[2];
 #pragma unroll
-      for (int d = 0; d < SD; ++d) gw[d] = 0.f;
+      for (int rn = 0; rn < 2; ++rn) dl[rn] = pr[r][rn] * (dP[rn][r] - dot);          // softmax backward
+      // in place: this lane owns the element.  (Two workgroups: the quadrant other queries x other keys is nobody's operand)
+      if (!SPLIT || (t >> 1) == rh || kh == rh) {
+#pragma unroll
+        for (int rn = 0; rn < 2; ++rn) sp[row * LDP + 32 * kh + 16 * rn + i] = dl[rn];
+      }
+      if (!SPLIT)
+        cond_grad_row(msr3d_attn::load_cond(scond, 8, L, row), plb + (size_t)row * L * SD, row < L, 32 * kh + i, dl, keyok,
+                      xg + (size_t)(kh * 64 + row) * 8, i == 0);
+    }
+    __syncthreads();                       // d S complete; one workgroup: the pairwise slab is dead, the cond partials visible
+    if (SPLIT) {
+      // the sigmoid part of the own queries: wave -> (own tile, key half, row pair): rows 2 rp, 2 rp + 1 of each row group
+      const int kh2 = (wave >> 1) & 1, rp = wave >> 2;
+      bool keyok2[2];
 #pragma unroll
       for (int rn = 0; rn < 2; ++rn) {
-        const int col = 32 * kh + 16 * rn + i;
-        const float dlogit = pr[r][rn] * (dP[rn][r] - dot);          // softmax backward
-        sp[row * LDP + col] = dlogit;                                // in place: this lane owns the element
-        if (row < L && keyok[rn]) {
-          const float *pl = plb + ((size_t)row * L + col) * SD;
-          float z = c.bias;
-#pragma unroll
-          for (int d = 0; d < SD; ++d) z = fmaf(c.w[d], pl[d], z);
-          const float loc = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-          const float dz = (loc >= 1e-6f) ? dlogit * (1.0f - loc) : 0.f;   // (attn_core.h: d log(max(loc, 1e-6)) / dz)
-          gb += dz;
-#pragma unroll
-          for (int d = 0; d < SD; ++d) gw[d] = fmaf(dz, pl[d], gw[d]);
-        }
+        const int col = 32 * kh2 + 16 * rn + i;
+        keyok2[rn] = col < L && !pad_b[min(col, L - 1)];
       }
-      gb = msr3d_attn::row16_sum(gb);
 #pragma unroll
-      for (int d = 0; d < SD; ++d) gw[d] = msr3d_attn::row16_sum(gw[d]);
-      if (i == 0) {
-        float *o = xg + (size_t)(kh * 64 + row) * 8;
-        o[0] = gb;
+      for (int r = 0; r < 2; ++r) {
+        const int row = q0 + 16 * (wave & 1) + 4 * g + 2 * rp + r;
+        float dl[2];
 #pragma unroll
-        for (int d = 0; d < SD; ++d) o[1 + d] = gw[d];
+        for (int rn = 0; rn < 2; ++rn) dl[rn] = sp[row * LDP + 32 * kh2 + 16 * rn + i];
+        cond_grad_row(msr3d_attn::load_cond(scond, 8, L, row), plb + (size_t)(row - q0) * L * SD, row < L, 32 * kh2 + i, dl,
+                      keyok2, xg + (size_t)(kh2 * 64 + row) * 8, i == 0);
       }
     }
-    __syncthreads();                       // d S complete; the pairwise slab is dead; the cond partials visible
     oq[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     ok[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    msr3d_attn::strip_mma<kCoreMma, 1, TM, true, false, true>(sp, LDP, sk + 16 * kh, LD32, row0, oq, lane);
-    msr3d_attn::strip_mma<kCoreMma, 1, TM, false, false, true>(sp, LDP, sq + 16 * kh, LD32, row0, ok, lane);
+    if (has_q) msr3d_attn::strip_mma<kCoreMma, 1, TM, true, false, true>(sp, LDP, sk + 16 * uc, LD32, urow0, oq, lane);
+    if (has_kv) msr3d_attn::strip_mma<kCoreMma, 1, TM, false, false, true>(sp, LDP, sq + 16 * uc, LD32, urow0, ok, lane);
+    if (SPLIT) __syncthreads();            // the pairwise slab is dead; the cond partials visible
   }
   SB_STAMP(6);
   // product 2's operand (FRAG planes, 4 slabs: [dq | dk | dv | dcond, 0]) on top of the dead pairwise slab; side outputs
   unsigned char *mid = reinterpret_cast<unsigned char *>(spl);
   {
-    const int row = row0 + j;
+    const int row = urow0 + j;
     const bool okr = row < L;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
+      if (a == 0 ? !has_q : !has_kv) continue;
       const f32x4 &src = a == 0 ? oq[0] : a == 1 ? ok[0] : ov[0];
       const float sc = a < 2 ? kInvSqrtDh : 1.0f;
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = okr ? src[r] * sc : 0.f;
-      if (okr) st4(p.dqkvc + (size_t)(row_base + row) * ldq + a * KD + h * DH + 16 * kh + 4 * g, make_float4(v[0], v[1], v[2], v[3]));
+      if (okr) st4(p.dqkvc + (size_t)(row_base + row) * ldq + a * KD + h * DH + 16 * uc + 4 * g, make_float4(v[0], v[1], v[2], v[3]));
       uint2 pl[3];
       sm_split4(v, pl);
 #pragma unroll
       for (int k = 0; k < 3; ++k)
-        *reinterpret_cast<uint2 *>(mid + frag_off4<4>(t, j, 32 * a + 16 * kh + 4 * g, k)) = pl[k];
+        *reinterpret_cast<uint2 *>(mid + frag_off4<4>(ut, j, 32 * a + 16 * uc + 4 * g, k)) = pl[k];
     }
   }
-  if (tid < TM) {                          // slab 3 of row `tid`: the six cond gradients (half 0 + half 1), zeros behind them
-    const int row = tid;
+  if (tid < NQ) {                          // slab 3 of an own row: the six cond gradients (half 0 + half 1), zeros behind them
+    const int row = q0 + tid;
     float dc[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) dc[c] = (row < L && c < SD + 1) ? xg[row * 8 + c] + xg[(64 + row) * 8 + c] : 0.f;
@@ -871,12 +963,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   }
   __syncthreads();
-  f32x4 acc2[2][4];
+  constexpr int MT2 = NQ / 16;             // the own row tiles (the other half's tiles of `mid` are never written)
+  f32x4 acc2[2][MT2];
   zero_acc3(acc2);
   const XFrag<4> xm{reinterpret_cast<const unsigned short *>(mid) + lane * 8};
-  gemm_split3<true, 2, 4, 4, RING>(xm, 0, w2, acc2, ring2);
+  gemm_split3<true, 2, MT2, 4, RING>(xm, q0 >> 4, w2, acc2, ring2);
   SB_STAMP(7);
-  store_partials<2>(acc2, slab, row_base, L, 32 * wave, lane);
+  store_partials<2, MT2>(acc2, slab, row_base, L, 32 * wave, lane, q0);
   SB_STAMP(8);
 }
 
@@ -1035,10 +1128,18 @@ int msr3d_scene_block(const msr3d_scene_block_t *pp, msr3d_stream_t stream) {
       if (p.H != 8 || !p.w2 || !p.qkvc || !p.dqkvc || !p.ploc || !p.pad || !p.probs || p.ldq % 4) return MSR3D_EINVAL;
       if (p.w1_bytes < 8u * 16u * kPieceBytes || p.w2_bytes < 8u * 4u * 16u * kPieceBytes) return MSR3D_EINVAL;
       {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd3_kernel),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kAttnBwd3Lds);
-        if (attr != hipSuccess) return (int)attr;
-        scene_attn_bwd3_kernel<<<dim3(8, p.B), 512, kAttnBwd3Lds, s>>>(p);
+        // one or two workgroups per (scene, head): the same bits either way.  Read at every call, so that one process can
+        // run both forms (a captured graph keeps the form it was captured with).
+        const char *form = std::getenv("MSR3D_ATTN_BWD_SPLIT");
+        const bool split = form && *form ? std::atoi(form) != 0 : MSR3D_ATTN_BWD_SPLIT_DEFAULT != 0;
+        static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd3_kernel<1>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, kAttnBwd3Lds);
+        static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void *>(&scene_attn_bwd3_kernel<2>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, kAttnBwd3Lds);
+        if (attr1 != hipSuccess) return (int)attr1;
+        if (attr2 != hipSuccess) return (int)attr2;
+        if (split) scene_attn_bwd3_kernel<2><<<dim3(16, p.B), 512, kAttnBwd3Lds, s>>>(p);
+        else scene_attn_bwd3_kernel<1><<<dim3(8, p.B), 512, kAttnBwd3Lds, s>>>(p);
         return (int)hipGetLastError();
       }
     case MSR3D_BLK_LINEAR:

@@ -37,7 +37,7 @@ def launch_block(stream, **kw):
     name = KIND[s.kind]
     slices = 8 if name.startswith("attn") else int(s.ff) // 128 if name.startswith("ffn") else \
         int(s.N) // 256 if name == "linear" else int(s.lda0) // 256
-    if name == "attn_fwd":
+    if name == "attn_fwd" or (name == "attn_bwd" and os.environ.get("MSR3D_ATTN_BWD_SPLIT", "1") not in ("", "0")):
         slices = 16                      # two workgroups per (scene, head)
     nblk = int(s.B) * slices
     wpb = max(len(st) // max(nblk, 1), 1)
